@@ -19,6 +19,13 @@ The other BASELINE configs are presets (not the driver's default line):
         active row violated by more than 1e-4; counts all-reduced over ranks)
 
 Prints ONE JSON line on rank 0 (see DESIGN.md §Measurement for the roofline / cpu_baseline fields).
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, the config and the roofline
+fields that come from the timed steps themselves).  `--full` adds the legs that take launches or CPU time of their own
+after the timed steps — feasible, roofline.latency, jacobian_sweep, closed_loop, cpu_baseline(_allcores); those
+fields are null without it.  `--dump-outputs DIR` writes the arrays the last timed step returned (u, foot, x_pred,
+status, iters; at N > 1 the rows gathered on rank 0) as DIR/<name>.npy: inputs come from --seed alone, so two builds
+run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -122,7 +129,32 @@ def parse():
                     help="cfg.restoration: IPOPT's restoration phase (default, the reference's) or the r1-r5 substitute")
     ap.add_argument("--closed-loop-steps", type=int, default=1,
                     help="walking steps of the per-tick closed-loop figure (f_cyc = 40 solves each; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take launches or CPU time of their own: the "
+                         "feasibility check, the latency probe, the Jacobian sweep, the closed loop and the CPU "
+                         "baselines (their fields are null in a plain run)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float64)")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: the per-instance arrays of the last timed step as d/<name>.npy in float64 (status / iters
+    converted).  At most DUMP_MAX_BYTES in all: a larger output is cut to a fixed seeded sample of its instances
+    (the same rows of every array, ascending; their indices go to d/sample_index.npy)."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    rows = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(v.nbytes // max(rows, 1) for v in arrays.values()) + 8
+    if rows * row_bytes > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(rows, size=DUMP_MAX_BYTES // row_bytes, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
 
 
 def main():
@@ -193,11 +225,21 @@ def main():
     stream = torch.cuda.current_stream(dev)
     solve = lambda: solver.solve_device(inp, out, stream=stream)  # noqa: E731
     step = make_step(solve, out, n, B_total_of(preset, args, B, world), rank, world, stream)
+    if args.dump_outputs and world > 1:   # keep what the last step's gather handed to rank 0
+        gather_step, gathered = step, [None]
+
+        def step(ev=None):
+            gathered[0] = gather_step(ev)
+            return gathered[0]
     elapsed, ev = timed_loop(step, args.warmup, args.steps, world, dev)
     K = args.steps
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     status = out["status"].cpu().numpy()
     iters = out["iters"].cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        # one GPU: the solve's output arrays; N > 1: the gathered [B_total, n + 5] rows (pack_outputs) on rank 0
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in out.items()} if world == 1 else
+                     {"gathered": gathered[0].cpu().numpy()})
     # lane program + IPOPT's restoration phase: instances whose line search failed are solved by the fp64 wave program
     try:
         handoffs = solver.lane_handoffs(stream) if program == "lane" else 0
@@ -232,17 +274,20 @@ def main():
 
     # quality beside the rate (every config): solves/s counts every instance, so report how many of them
     # converged and how many returned plans are feasible for the reference constraints
-    feas = feasible_fraction(alipmpc, solver, cfg, inp, out, dev, world, dist)
+    # (--full, like every leg below: each takes launches or CPU time of its own after the timed steps)
+    full = args.full
+    feas = feasible_fraction(alipmpc, solver, cfg, inp, out, dev, world, dist) if full else None
 
     # the wave program's binding resource is the per-iteration dependency chain of its slowest instances (MFMA busy
     # ~0.05, VALU issue ~0.5): the critical instance's iteration time alone on its SIMD, live, against the issue floor
-    lat = latency_probe(solver, inp, out, iters, prof, dev) if (rank == 0 and program == "wave") else None
-    sweep = jacobian_sweep(alipmpc, scenes, variant, args, dev) if (rank == 0 and args.sweep_batch > 0) else None
+    lat = latency_probe(solver, inp, out, iters, prof, dev) if (full and rank == 0 and program == "wave") else None
+    sweep = jacobian_sweep(alipmpc, scenes, variant, args, dev) \
+        if (full and rank == 0 and args.sweep_batch > 0) else None
     cl = closed_loop_rate(solver, inp, out, args.closed_loop_steps, dev) \
-        if (rank == 0 and args.closed_loop_steps > 0) else None
+        if (full and rank == 0 and args.closed_loop_steps > 0) else None
 
     cpu = cpu_mt = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(cfg, batch, args.cpu_seconds, workload=args.config)
         # the same C restatement with OpenMP over the host cores this job may use (batches that give
         # every thread at least one 64-instance chunk)
@@ -257,6 +302,7 @@ def main():
             "n_gpus": world,
             "steps": K,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": elapsed / K * 1e3,
             "higher_is_better": True,
             "scaling": "weak" if preset["per_gpu"] or args.batch is not None else "strong",

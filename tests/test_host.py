@@ -274,3 +274,29 @@ def test_bench_bound_label_from_counters():
     assert bench.bound_label("lane", {"mfma_busy_share": 0.0, "valu_issue_frac": 0.396}) == "latency"     # cfg4
     assert bench.bound_label("wave", {"mfma_busy_share": 0.6, "valu_issue_frac": 0.7}) == "mfma"
     assert bench.bound_label("lane", {}) == "valu" and bench.bound_label("wave", {}) == "latency"
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array as float64 DIR/<name>.npy; above the size cap the same fixed, seeded,
+    ascending sample of instances of every array (indices in sample_index.npy), identical from run to run."""
+    import bench
+    B = 50
+    arrays = {"u": np.arange(B * 15, dtype=np.float64).reshape(B, 15), "foot": np.ones((B, 3)),
+              "status": np.arange(B, dtype=np.int32), "iters": np.full(B, 7, np.int32)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in arrays}
+    assert not (tmp_path / "a" / "sample_index.npy").exists()
+    for k, v in arrays.items():
+        assert got[k].dtype == np.float64 and np.array_equal(got[k], v)
+    row = (15 + 3 + 1 + 1 + 1) * 8                    # bytes per instance, the index included
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 20 * row + 5)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    bench.dump_outputs(str(tmp_path / "c"), arrays)
+    idx = np.load(tmp_path / "b" / "sample_index.npy").astype(np.int64)
+    assert idx.shape == (20,) and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < B
+    total = 0
+    for k, v in arrays.items():
+        s = np.load(tmp_path / "b" / (k + ".npy"))
+        assert np.array_equal(s, v[idx]) and np.array_equal(s, np.load(tmp_path / "c" / (k + ".npy")))
+        total += s.nbytes
+    assert total + idx.size * 8 <= bench.DUMP_MAX_BYTES

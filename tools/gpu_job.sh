@@ -4,7 +4,7 @@
 #   pytest:EXPR      pytest -m gpu -k EXPR (EXPR "all": the whole GPU suite), stop at the first failure
 #   survey:EXPR      the same, up to 40 failures (a survey of what a change broke)
 #   smoke            __graft_entry__.smoke()
-#   bench[:ARGS]     bench.py ARGS (default line with no args)
+#   bench[:ARGS]     bench.py ARGS (the plain default line with no args; pass --full for the other legs)
 #   gpurun:...       any tools/gpu_run.sh step list (tests bench configs prof wst), comma-separated
 # Every GPU step has its own time limit; the chain stops at the first failure.
 set -u

@@ -26,12 +26,12 @@ for what in "$@"; do
     cat $OUT/smoke.log ;;
   bench)
     echo "=== bench (default = cfg2)"
-    timeout -k 10 300 python $R/bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+    timeout -k 10 300 python $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
     cat $OUT/bench.json ;;
   configs)
     for c in ${CONFIGS:-cfg3 cfg4 cfg5 cfg1}; do
       echo "=== bench $c"
-      timeout -k 10 400 python $R/bench.py --config $c --steps 5 --cpu-seconds 5 --sweep-batch 0 > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { tail -20 $OUT/bench_$c.err; exit 1; }
+      timeout -k 10 400 python $R/bench.py --full --config $c --steps 5 --cpu-seconds 5 --sweep-batch 0 > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { tail -20 $OUT/bench_$c.err; exit 1; }
       python -c "import json;d=json.load(open('$OUT/bench_$c.json'));print('$c', round(d['value']), d['ms_per_step'], d['config']['mean_iters'], d.get('feasible'), d['cpu_baseline']['value'])"
     done ;;
   prof)
@@ -52,7 +52,7 @@ for what in "$@"; do
       fi
       flags="--config $c --no-cpu-baseline --closed-loop-steps 0 --sweep-batch 0"
       echo "=== bench $c"
-      timeout -k 10 300 python3 $R/bench.py $flags --steps 10 > $D/bench.json 2> $D/bench.err || { tail -20 $D/bench.err; exit 1; }
+      timeout -k 10 300 python3 $R/bench.py --full $flags --steps 10 > $D/bench.json 2> $D/bench.err || { tail -20 $D/bench.err; exit 1; }
       echo "=== rocprofv3 kernel trace $c"
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D/prof_kt -o kt -- python3 $R/bench.py $flags --steps 10 > $D/prof_kt.log 2>&1 || { tail -20 $D/prof_kt.log; exit 1; }
       for pmc in "${PMCS[@]}"; do
