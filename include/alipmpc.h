@@ -23,7 +23,8 @@
  *     hip_stream != NULL: all pointers are DEVICE pointers (hipMalloc / torch CUDA tensors) and the call
  *     is asynchronous on that stream (no host synchronisation; graph-capturable).  The only device allocation
  *     is the split launch's record buffer (alipmpc_solve_launches): one per stream, made by the stream's first
- *     split solve, sized for the resident slots and kept until alipmpc_destroy — a capture on a stream that has
+ *     split solve, sized for the resident slots (per slot one loop-state record and three index words: the record's
+ *     instance and the two class lists of the paired phase 2) and kept until alipmpc_destroy — a capture on a stream that has
  *     none yet records the one-phase form.  A captured graph uses its capture stream's buffer: replay it on that
  *     stream (or ordered with the solves there).  At most 8 streams per handle hold one (kept until destroy, never
  *     evicted); solves on a further stream run the one-phase form (same bits).  ALIPMPC_STREAM_NULL selects device pointers on
@@ -313,6 +314,12 @@ int alipmpc_solve_slots(void* handle, int64_t* slots);
  * unfinished instances from their exact loop-state records — or, fp64, ALIPMPC_SPLIT_TR > 0), 1 otherwise; *team = the
  * team size (4 waves) when phase 1 also cuts instances by their line-search trial count (ALIPMPC_SPLIT_TR > 0, fp64
  * only) into team records that phase 2 runs on a team each, else 1.
+ * fp64 with cfg.restoration = ALIPMPC_RESTORATION_IPOPT, no team records, one row group per lane and 8 workspaces within
+ * the LDS (cfg2's shape): phase 2 is the PAIRED form, still one launch — phase 1 lists its records in two classes (cut
+ * with a restoration pending / cut at the iteration cap), and phase 2 runs 8-wave workgroups, two waves per SIMD, whose
+ * owner waves 0-3 resume the pending-restoration records at top priority and whose filler waves 4-7 resume regular
+ * ones, so no SIMD holds two restoration tails while another holds none.  ALIPMPC_SPLIT_PAIR=0 selects the 4-wave
+ * phase 2 with the records in cut order (same bits either way).  The closed loop's per-tick solves keep the 4-wave form.
  * It reports the form of an eager launch on a stream that holds, or can still get, a record buffer: a launch
  * captured into a graph on a stream without one, or on a ninth stream, runs the one-phase form (1 launch).
  * Profiling tools use it to turn per-dispatch figures into per-solve ones.  No reference counterpart. */

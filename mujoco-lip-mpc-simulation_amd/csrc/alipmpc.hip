@@ -91,7 +91,8 @@ struct KP {
                             // order[k]; the closed loop puts last tick's long instances first)
     int ckpt_it;            // split launch, phase 1 (> 0): an instance still running at this iteration saves its
                             // loop state to a record and stops (solve_kernel, one wave per instance)
-    int resume;             // split launch, phase 2: wave k resumes the instance of record k
+    int resume;             // split launch, phase 2: wave k resumes the instance of record k (2: the paired form —
+                            // 8-wave workgroups, pending-restoration records on the owner waves, solve_kernel)
     int ckpt_tr;            // split launch, phase 1 (> 0, with team > 0): an instance whose line search has run this
                             // many trials also stops (before ckpt_it) and gets a TEAM record
     int team;               // split launch (team-capable build): phase 1 — team records on (ckpt_tr); phase 2 — team
@@ -142,6 +143,10 @@ constexpr int SPLIT_IT_DEFAULT = ALIP_SPLIT_IT;   // phase-1 iteration cap of th
 // instances reach phase 2 earlier; sweep on cfg2: 12 / 13 / 14 / 15 / 16 / 17 / 18 / 20 = 0.636 / 0.630 / 0.646 /
 // 0.653 / 0.613 / 0.626 / 0.641 / 0.650 ms)
 constexpr int SPLIT_IT_DEFAULT_RESTO = 16;
+// and with the paired phase 2 (r7, solve_kernel<..., PR>: the pending restorations own their SIMDs, so a lower cut no
+// longer stacks two of them; sweep on cfg2, 9 ... 16 = 0.788 / 0.739 / 0.692 / 0.613 / 0.565 / 0.591 / 0.598 / 0.612 ms
+// against 0.609 ms for the 4-wave form at 16, profiles/r7/split_cut_pair.log)
+constexpr int SPLIT_IT_DEFAULT_RESTO_PAIR = 13;
 constexpr int SPLIT_TR_DEFAULT = 0;               // phase-1 trial cut of a cold solve (0 = off: no team records)
 constexpr int CL_SPLIT_IT_DEFAULT = 20;           // the closed loop's per-tick solves: phase-1 cap (r5: 16 / 18 / 20 / 22 /
                                                    // 24 = 23.7 / 22.95 / 22.7 / 22.8 / 23.6 ms per loop)
@@ -152,9 +157,19 @@ static int env_groups()
     const char* t = std::getenv("ALIPMPC_CL_GROUPS");
     return t ? std::max(1, std::atoi(t)) : CL_GROUPS_DEFAULT;
 }
-// split-launch counters (KP.cont): single records, team records, then the B instance ids of records (index k)
-constexpr int CONT_SINGLE = 0, CONT_TEAM = 1;
-__host__ __device__ constexpr long long cont_hdr(long long) { return 2; }
+// split-launch counters (KP.cont): single records, team records, then the B instance ids of records (index k).
+// r7, fp64: the single records come in two classes — cut with a restoration pending (CONT_PEND) and cut at the
+// iteration cap (CONT_REG) — each with an index list of its records' k (cont_list), so the paired phase 2 can tell
+// them apart before it assigns waves.  The record slots themselves stay in cut order (CONT_SINGLE).
+constexpr int CONT_SINGLE = 0, CONT_TEAM = 1, CONT_PEND = 2, CONT_REG = 3;
+__host__ __device__ constexpr long long cont_hdr(long long) { return 4; }
+// entry i of a class list (cls = CONT_PEND / CONT_REG) of a B-instance launch
+__host__ __device__ constexpr long long cont_list(long long B, int cls, long long i)
+{
+    return cont_hdr(B) + (cls == CONT_PEND ? 1 : 2) * B + i;
+}
+constexpr long long CONT_WORDS_PER_SLOT = 3;   // instance ids + the two class lists
+constexpr int PAIR_WAVES = 8;   // waves of a paired phase-2 workgroup: owners 0-3, fillers 4-7 (wave w and w + 4 share a SIMD)
 constexpr long long TEAM_CAP = 128;   // team workgroups of a phase-2 launch (team records beyond run one wave each)
 // waves of a team-capable workgroup = members of a team, each testing one of that many consecutive line-search trials
 // per round.  r5 measured 8 against 4: the closed loop 33.8 vs 31.1 ms — every member also
@@ -234,7 +249,7 @@ __device__ unsigned long long g_stamps[NSTAMP];
 
 // ---- diagnostic per-instance record of the wave program (compiled only with -DALIP_WSTAMP; never in the product
 // build): [start, end] of the instance on the constant 100 MHz clock and the shader clock, HW_ID / XCC_ID of the wave,
-// iterations, line-search trials, restorations.  Slot = g_wstamp_base + instance (the closed loop sets the base per
+// iterations, line-search trials, restorations (bit 32: resumed with a restoration pending).  Slot = g_wstamp_base + instance (the closed loop sets the base per
 // tick), 8 values per slot, written by lanes 0..7 (vector stores).  tools/cl_wstamps.py reads it.
 #ifdef ALIP_WSTAMP
 constexpr long long WSTAMP_CAP = 48 * 4096;
@@ -243,8 +258,10 @@ __device__ long long g_wstamp_base;
 #define WSTAMP_DECL                                                                        \
     const unsigned long long ws_t0 = __builtin_amdgcn_s_memrealtime();                    \
     const unsigned long long ws_c0 = __builtin_amdgcn_s_memtime();                        \
-    unsigned ws_trials = 0;
+    unsigned ws_trials = 0;                                                                \
+    unsigned ws_pend = 0;
 #define WSTAMP_TRIAL ++ws_trials
+#define WSTAMP_PEND(x) ws_pend = (x) ? 1u : 0u   /* a phase-2 wave that resumes a pending-restoration record */
 #define WSTAMP_WRITE(b, it, nrest)                                                         \
     do {                                                                                   \
         const unsigned long long t1_ = __builtin_amdgcn_s_memrealtime();                   \
@@ -256,12 +273,13 @@ __device__ long long g_wstamp_base;
         unsigned long long v_ = l_ == 0 ? ws_t0 : l_ == 1 ? t1_ : l_ == 2 ? ws_c0 : l_ == 3 ? c1_ \
                               : l_ == 4 ? ((unsigned long long)xcc_ << 32 | hw_)                \
                               : l_ == 5 ? (unsigned long long)(it) : l_ == 6 ? (unsigned long long)ws_trials \
-                              : (unsigned long long)(nrest);                               \
+                              : ((unsigned long long)(nrest) | (unsigned long long)ws_pend << 32); \
         if (slot_ >= 0 && slot_ < WSTAMP_CAP && l_ < 8) g_wstamp[slot_ * 8 + l_] = v_;     \
     } while (0)
 #else
 #define WSTAMP_DECL
 #define WSTAMP_TRIAL do {} while (0)
+#define WSTAMP_PEND(x) do {} while (0)
 #define WSTAMP_WRITE(b, it, nrest) do {} while (0)
 #endif
 
@@ -1322,11 +1340,15 @@ constexpr bool TEAM_HANDOVER = 3 * WAVE * RPL + 3 <= Dim<N>::NCP * Dim<N>::KLD;
 // (resto_wave.inc, inlined) at the top of the next iteration.  The lean build (RS = false: phase 1 of a split launch)
 // instead cuts the instance to a split record flagged "restoration pending", and phase 2's RS build runs the phase
 // first — so the restoration's registers never touch the lean loop that most instances finish in.
-template <int N, int KSM, class R, bool Q, bool TM = false, bool RS = false>
+// PR: the paired phase-2 build (solve_kernel<..., PR = true>): role 1 = an owner wave, which keeps the top priority
+// for its whole resume; role 2 = a filler wave, whose iteration-based priority stays below the owners' until a
+// restoration of its own.  Without PR the role compiles out.
+template <int N, int KSM, class R, bool Q, bool TM = false, bool RS = false, bool PR = false>
 __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, long long b, long long rec = -1,
-                                          int tm = 0)
+                                          int tm = 0, int role = 0)
 {
     if constexpr (!TM) tm = 0;
+    if constexpr (!PR) role = 0;
     // Q (persistent instance loop): opaque per-instance copies of the lane-/wave-derived inputs, so that
     // nothing computed from them is loop-invariant and no address or row table is hoisted out of the
     // instance loop (and spilled).  (Laundering the LDS base offsets as well cut the scratch further but
@@ -1597,6 +1619,7 @@ __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, lo
         theta_ok = rfl((int)sc[10]) != 0;
         if constexpr (RS) {   // (a lean-build record: the restoration pending at its point)
             rpend = rfl((int)sc[11]) != 0;
+            WSTAMP_PEND(rpend);
             theta_R = uni(ck_get<R>(sc[12]));
         }
         if (lane < NG) w.V[lane] = vme;
@@ -1604,7 +1627,9 @@ __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, lo
 #ifndef ALIP_NO_SETPRIO
         // (a team is the critical path of its launch by construction — the instance whose line searches ran long —
         // and in the closed loop it shares SIMDs with the other episode group's phase 1: top priority)
-        if (it0 >= 20 || (TM && tm < 0))
+        // (paired phase 2: an owner wave is on the critical path too — a restoration tail, or a SIMD of its own; a
+        // filler stays below it until it has restored itself)
+        if ((PR && role == 1) || (it0 >= 20 && !(PR && role == 2 && n_rest == 0)) || (TM && tm < 0))
             __builtin_amdgcn_s_setprio(3);
         else if (it0 >= 14)
             __builtin_amdgcn_s_setprio(2);
@@ -1661,6 +1686,12 @@ __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, lo
         for (int i = 0; i < 13; ++i) v = lane == i ? sv[i] : v;
         if (lane < 13) rc[ck_scal(mo4) + lane] = v;
         if (lane == 0) P.cont[cont_hdr(P.B) + k] = (uint32_t)b;
+        if constexpr (sizeof(R) == 8) {   // the record's class list (the paired phase 2 is fp64 only)
+            if (lane == 0 && !to_team) {
+                const int cls = rp ? CONT_PEND : CONT_REG;
+                P.cont[cont_list(P.B, cls, (long long)atomicAdd(P.cont + cls, 1u))] = (uint32_t)k;
+            }
+        }
     };
     R phi_R = R(0.0);
     it = it0;
@@ -1672,6 +1703,9 @@ __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, lo
             // IPOPT's restoration phase from the failed point (the current iterate, slacks and multipliers; the
             // augmented filter; theta_R), resto_wave.inc; its iterate comes back through the workspace
             rpend = false;
+#ifndef ALIP_NO_SETPRIO
+            if (PR && role == 2) __builtin_amdgcn_s_setprio(3);   // (a filler's own restoration: a tail like its owner's)
+#endif
             STAMP(8);
             RELANE();
 #pragma unroll
@@ -1742,8 +1776,11 @@ __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, lo
         // that have run long get priority, so the critical (high-iteration) instances run closer to their
         // lone-wave latency while the short ones, which have slack, yield.
 #ifndef ALIP_NO_SETPRIO
-        if (TM && tm < 0)
-            ;   // a team member keeps the top priority it resumed with
+        if ((TM && tm < 0) || (PR && (role == 1 || (role == 2 && n_rest > 0))))
+            ;   // a team member / a paired owner keeps the top priority it resumed with (a filler: the one its
+                // own restoration raised it to)
+        else if (PR && role == 2 && it == 20)
+            ;   // a paired filler that has not restored stays below its SIMD's owner
         else if (it == 8)
             __builtin_amdgcn_s_setprio(1);
         else if (it == 14)
@@ -2592,14 +2629,33 @@ constexpr int solve_waves()
 // solve_one and produce the same bits for an instance (test_work_queue_batch_independence solves a batch
 // above the slots whole and in half-slot chunks and compares status, iters, u, foot, x_pred exactly), so an
 // instance's result does not depend on its batch or on the device's slot count.
-template <int N, int KSM, class R, bool ONE, bool TM = false, bool RS = false>
-__global__ __launch_bounds__(WAVE * (TM ? TEAM_WAVES : WAVES_PER_BLOCK), (solve_waves<KSM, R, RS>())) void solve_kernel(KP Pv)
+//
+// PR: the paired phase 2 of a split launch (fp64, cfg.restoration = IPOPT, no team records; Pv.resume = 2).  A
+// workgroup has PAIR_WAVES = 8 waves, two per SIMD (waves w and w + 4 share one), and fills a CU's occupancy of the
+// restoration-capable build, so which records share a SIMD is decided here and not by the dispatch order.  With
+// np pending-restoration and nr regular records (the class lists phase 1 wrote), P4 = np rounded up to 4:
+//   workgroup j < P4 / 4:  owner wave w < 4 resumes pending record 4 j + w, or — beyond np — regular record
+//                          P4 + (4 j + w - np); filler wave w >= 4 resumes regular record 4 j + (w - 4)
+//   workgroup j >= P4 / 4: wave w resumes regular record 2 P4 - np + 8 (j - P4 / 4) + w
+// so no SIMD holds two pending records while another holds none, every pending record starts in the first
+// dispatched workgroups, and a workgroup without a record exits before it stages anything.
+template <int N, int KSM, class R, bool ONE, bool TM = false, bool RS = false, bool PR = false>
+__global__ __launch_bounds__(WAVE * (TM ? TEAM_WAVES : PR ? PAIR_WAVES : WAVES_PER_BLOCK), (solve_waves<KSM, R, RS>())) void solve_kernel(KP Pv)
 {
+    static_assert(!PR || (ONE && RS && !TM && sizeof(R) == 8), "the paired form: fp64 restoration-capable phase 2");
     constexpr int WPB = TM ? TEAM_WAVES : WAVES_PER_BLOCK;   // waves per workgroup (team-capable: the team size)
     using D = Dim<N>;
     constexpr int NCP = D::NCP;
     constexpr int NG = D::NG;
     extern __shared__ __attribute__((aligned(16))) double smem[];
+    long long pr_np = 0, pr_nr = 0, pr_p4 = 0;
+    if constexpr (PR) {
+        pr_np = (long long)__builtin_amdgcn_readfirstlane(Pv.cont[CONT_PEND]);
+        pr_nr = (long long)__builtin_amdgcn_readfirstlane(Pv.cont[CONT_REG]);
+        pr_p4 = (pr_np + 3) & ~3ll;
+        const long long j = (long long)blockIdx.x;
+        if (j >= pr_p4 / 4 && 2 * pr_p4 - pr_np + PAIR_WAVES * (j - pr_p4 / 4) >= pr_nr) return;   // (the whole workgroup)
+    }
     KP* Ps = reinterpret_cast<KP*>(smem);
     R* G = reinterpret_cast<R*>(smem + KP_DOUBLES);
     // (r4: no LDS copy of E — the prologue reads it from global memory once per instance)
@@ -2619,6 +2675,29 @@ __global__ __launch_bounds__(WAVE * (TM ? TEAM_WAVES : WAVES_PER_BLOCK), (solve_
         const bool team = (long long)blockIdx.x < nteamwg;
         const long long k = team ? (long long)blockIdx.x : ((long long)blockIdx.x - nteamwg) * WPB + wv;
         long long b = -1, rec = -1;   // one inlined solve_one for every form (the code is large)
+        int role = 0;
+        if constexpr (PR) {   // the paired phase 2 (above): this wave's record, through its class list
+            const long long j = (long long)blockIdx.x, jp = pr_p4 / 4;
+            role = wv < 4 ? 1 : 2;
+            long long li = -1;   // index into the regular list, unless pend
+            bool pend = false;
+            if (j < jp) {
+                const long long o = 4 * j + wv;
+                if (wv >= 4)
+                    li = o - 4;
+                else if (o < pr_np) {
+                    pend = true;
+                    li = o;
+                } else
+                    li = pr_p4 + (o - pr_np);
+            } else {
+                li = 2 * pr_p4 - pr_np + PAIR_WAVES * (j - jp) + wv;
+            }
+            if (pend || li < pr_nr) {
+                rec = (long long)__builtin_amdgcn_readfirstlane(Pv.cont[cont_list(Pv.B, pend ? CONT_PEND : CONT_REG, li)]);
+                b = (long long)__builtin_amdgcn_readfirstlane(Pv.cont[cont_hdr(Pv.B) + rec]);
+            }
+        } else
         if (Pv.resume) {   // split launch, phase 2
             const long long made = TM ? (long long)__builtin_amdgcn_readfirstlane(Pv.cont[CONT_TEAM]) : 0;
             if (team) {
@@ -2639,7 +2718,7 @@ __global__ __launch_bounds__(WAVE * (TM ? TEAM_WAVES : WAVES_PER_BLOCK), (solve_
         rec = __builtin_amdgcn_readfirstlane((int)rec);
         // (one call site: the team solves run the very machine code of the single ones — two inlined copies had
         // rounded differently)
-        if (b >= 0) solve_one<N, KSM, R, false, TM, RS>(P, G, wsb, wv, b, rec, team ? -1 - wv : 0);
+        if (b >= 0) solve_one<N, KSM, R, false, TM, RS, PR>(P, G, wsb, wv, b, rec, team ? -1 - wv : 0, role);
     } else {
         uint32_t* const q = Pv.queue;
         // (a hand-off launch: the count of the list it solves was written on the device by the launch before it)
@@ -4835,6 +4914,16 @@ size_t team_smem(size_t smem)
     return fixed + (smem - fixed) / WAVES_PER_BLOCK * TEAM_WAVES;
 }
 
+// the paired phase-2 build's workgroup LDS: PAIR_WAVES workspaces (fp64)
+template <int N>
+size_t pair_smem(size_t smem)
+{
+    const size_t fixed = sizeof(double) * ((size_t)KP_DOUBLES + (size_t)Dim<N>::NG * Dim<N>::NCP);
+    return fixed + (smem - fixed) / WAVES_PER_BLOCK * PAIR_WAVES;
+}
+// (compiled for the shapes with one row group per lane, the 2-waves-per-SIMD restoration-capable builds)
+constexpr bool pair_ksm(int ksm) { return 4 * ksm <= WAVE; }
+
 template <int N, class R>
 void launch_solve(const KP& P0, size_t smem, hipStream_t st, unsigned* res_out)
 {
@@ -4844,7 +4933,17 @@ void launch_solve(const KP& P0, size_t smem, hipStream_t st, unsigned* res_out)
     const unsigned need_t = (P0.resume ? (unsigned)P0.team : 0u) + (unsigned)((P0.B + TEAM_WAVES - 1) / TEAM_WAVES);
     const size_t smem_t = team_smem<N, R>(smem);
     // KSM = 4-row steps of the J layout, the smallest compiled size covering mo4 rows
-    auto go = [&](auto kq, auto k1, auto kt) {
+    auto go = [&](auto kq, auto k1, auto kt, auto kp) {
+        if constexpr (!std::is_same_v<decltype(kp), std::nullptr_t>) {
+            if (P0.resume == 2 && !res_out) {
+                // the paired phase 2 (alipmpc_create checked that its workgroup fits the LDS): the worst-case grid —
+                // ceil(np / 4) workgroups with pending records, then 8 regular records each, np + nr <= B
+                const size_t smem_p = pair_smem<N>(smem);
+                set_smem((const void*)kp, smem_p);
+                hipLaunchKernelGGL(kp, dim3((unsigned)((P0.B + 3) / 4) + 1u), dim3(WAVE * PAIR_WAVES), smem_p, st, P0);
+                return;
+            }
+        }
         set_smem((const void*)kq, smem);
         set_smem((const void*)k1, smem);
         // (the team-capable build runs only where its workgroup fits the LDS: alipmpc_create clears the trial cuts
@@ -4871,13 +4970,19 @@ void launch_solve(const KP& P0, size_t smem, hipStream_t st, unsigned* res_out)
 #define ALIP_GO(K)                                                                                              \
     do {                                                                                                        \
         if constexpr (sizeof(R) == 8) {                                                                         \
-            if (rs)                                                                                             \
-                go(solve_kernel<N, K, R, false, false, true>, solve_kernel<N, K, R, true, false, true>,         \
-                   solve_kernel<N, K, R, true, true, true>);                                                    \
-            else                                                                                                \
-                go(solve_kernel<N, K, R, false>, solve_kernel<N, K, R, true>, solve_kernel<N, K, R, true, true>); \
+            if (rs) {                                                                                           \
+                if constexpr (pair_ksm(K))                                                                      \
+                    go(solve_kernel<N, K, R, false, false, true>, solve_kernel<N, K, R, true, false, true>,     \
+                       solve_kernel<N, K, R, true, true, true>, solve_kernel<N, K, R, true, false, true, true>); \
+                else                                                                                            \
+                    go(solve_kernel<N, K, R, false, false, true>, solve_kernel<N, K, R, true, false, true>,     \
+                       solve_kernel<N, K, R, true, true, true>, nullptr);                                       \
+            } else                                                                                              \
+                go(solve_kernel<N, K, R, false>, solve_kernel<N, K, R, true>, solve_kernel<N, K, R, true, true>, \
+                   nullptr);                                                                                    \
         } else {                                                                                                \
-            go(solve_kernel<N, K, R, false>, solve_kernel<N, K, R, true>, solve_kernel<N, K, R, true, false>);  \
+            go(solve_kernel<N, K, R, false>, solve_kernel<N, K, R, true>, solve_kernel<N, K, R, true, false>,   \
+               nullptr);                                                                                        \
         }                                                                                                       \
     } while (0)
 #ifdef ALIP_DEV_ONLY_KSM   // dev builds for register reports (tools/regs.py): one row-step count only
@@ -5120,6 +5225,9 @@ struct Handle {
     int split_it = 0;
     int split_tr = 0;   // phase-1 trial cut: an instance at this many line-search trials resumes as a team (0 = off)
     int cl_split_it = 0, cl_split_tr = 0;   // the closed loop's per-tick solves (ALIPMPC_CL_SPLIT_IT / _TR)
+    // the paired phase 2 of the batch API's split (ALIPMPC_SPLIT_PAIR=0 turns it off): fp64 wave program with
+    // cfg.restoration = IPOPT, one row group per lane, 8 workspaces within the LDS; only without team records
+    bool split_pair = false;
     // Record buffers are sized ONCE for the resident slots (the largest batch that splits) and never reallocated or
     // freed before alipmpc_destroy, so a graph captured on a stream keeps a valid pointer whatever batch sizes run on
     // that stream later.  At most SPLIT_STREAMS of them: a further stream runs the one-phase form.
@@ -5762,6 +5870,19 @@ int alipmpc_create(const alipmpc_cfg* cfg, int device, void** handle)
 #undef TSCASE
         }
         if (st_ > 160 * 1024) h->split_tr = h->cl_split_tr = 0;
+        // the paired phase 2 (solve_kernel<..., PR>): where its 8 workspaces fit; it has a cut of its own
+        size_t sp_ = 0;
+        switch (h->N) {
+#define PSCASE(NN) \
+    case NN: sp_ = pair_smem<NN>(smem_bytes(h, true)); break;
+            PSCASE(1) PSCASE(2) PSCASE(3) PSCASE(4) PSCASE(5) PSCASE(6)
+#undef PSCASE
+        }
+        const char* pe = std::getenv("ALIPMPC_SPLIT_PAIR");
+        h->split_pair = !(pe && std::atoi(pe) == 0) && cfg->restoration == ALIPMPC_RESTORATION_IPOPT &&
+                        pair_ksm(h->mo4 / 4) && sp_ <= 160 * 1024;
+        if (h->split_pair && !std::getenv("ALIPMPC_SPLIT_IT") && SPLIT_IT_DEFAULT_RESTO_PAIR < h->cfg.max_iter)
+            h->split_it = SPLIT_IT_DEFAULT_RESTO_PAIR;
     }
     *handle = h;
     return ALIPMPC_OK;
@@ -5817,7 +5938,8 @@ static void* split_buffer(Handle* h, hipStream_t st, size_t need, hipError_t& er
     return it->second.p;
 }
 
-static hipError_t launch_solve(Handle* h, const KP& P, hipStream_t st, int split_it, int split_tr)
+// pair: the paired phase 2 where it applies (the batch API; the closed loop's per-tick solves keep the 4-wave form)
+static hipError_t launch_solve(Handle* h, const KP& P, hipStream_t st, int split_it, int split_tr, bool pair = false)
 {
     const alipmpc_cfg& cf = h->cfg;
     if (cf.precision == ALIPMPC_PREC_FP32) split_tr = 0;   // (the team-capable build is fp64 only)
@@ -5829,7 +5951,8 @@ static hipError_t launch_solve(Handle* h, const KP& P, hipStream_t st, int split
     // records for the slots, not for this B: the buffer of a stream never changes size
     const size_t rec_bytes = ((size_t)slots * ckpt_doubles(h->mo4) * sizeof(double) + 255) & ~(size_t)255;
     const size_t hdr = (size_t)cont_hdr(slots);
-    const size_t need = rec_bytes + (hdr + (size_t)slots) * sizeof(uint32_t);
+    // (instance ids and the two class lists of the single records)
+    const size_t need = rec_bytes + (hdr + (size_t)CONT_WORDS_PER_SLOT * (size_t)slots) * sizeof(uint32_t);
     hipError_t berr = hipSuccess;
     void* buf = split_buffer(h, st, need, berr);
     if (berr != hipSuccess) return berr;
@@ -5845,7 +5968,7 @@ static hipError_t launch_solve(Handle* h, const KP& P, hipStream_t st, int split
     P1.cont = cont;
     if (hipError_t e = launch(h, true, P1, st)) return e;
     KP P2 = P;   // single records, and team records
-    P2.resume = 1;
+    P2.resume = pair && h->split_pair && team == 0 && cf.precision != ALIPMPC_PREC_FP32 ? 2 : 1;
     P2.team = team;
     P2.ckpt = (double*)buf;
     P2.cont = cont;
@@ -5882,7 +6005,7 @@ static int run_batch(Handle* h, bool solve, int64_t B, const double* x0, const d
         const int ei = h->evi;
         h->evi = (ei + 1) % Handle::NEV;
         HIPCHK(h, hipEventRecord(h->ev[ei][0], st));
-        HIPCHK(h, solve ? launch_solve(h, P, st, h->split_it, h->split_tr) : launch(h, false, P, st));
+        HIPCHK(h, solve ? launch_solve(h, P, st, h->split_it, h->split_tr, true) : launch(h, false, P, st));
         HIPCHK(h, hipEventRecord(h->ev[ei][1], st));
         h->evlast = ei;
         h->timed = true;
@@ -5964,7 +6087,7 @@ static int run_batch(Handle* h, bool solve, int64_t B, const double* x0, const d
     const int ei = h->evi;
     h->evi = (ei + 1) % Handle::NEV;
     HIPCHK(h, hipEventRecord(h->ev[ei][0], st));
-    HIPCHK(h, solve ? launch_solve(h, P, st, h->split_it, h->split_tr) : launch(h, false, P, st));
+    HIPCHK(h, solve ? launch_solve(h, P, st, h->split_it, h->split_tr, true) : launch(h, false, P, st));
     HIPCHK(h, hipEventRecord(h->ev[ei][1], st));
     h->evlast = ei;
     h->timed = true;

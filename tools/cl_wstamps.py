@@ -49,7 +49,9 @@ def summarize(rec, active=None, tag=""):
     base = t0.min()
     st, en = (t0 - base) / 100.0, (t1 - base) / 100.0      # microseconds
     dur = en - st
-    its, trials, rest = r[:, 5].astype(np.int64), r[:, 6].astype(np.int64), r[:, 7].astype(np.int64)
+    its, trials = r[:, 5].astype(np.int64), r[:, 6].astype(np.int64)
+    # (restorations in the low word; bit 32: a phase-2 wave that resumed a pending-restoration record)
+    rest, pend = (r[:, 7] & 0xFFFFFFFF).astype(np.int64), ((r[:, 7] >> 32) & 1).astype(bool)
     hw = (r[:, 4] & 0xFFFFFFFF).astype(np.int64)
     xcc = (r[:, 4] >> 32).astype(np.int64)
     keys = np.array([simd_key(h, x) for h, x in zip(hw, xcc)])
@@ -77,6 +79,16 @@ def summarize(rec, active=None, tag=""):
                      "simd_trials": int(per_simd_tr[inv[crit]])},
         "started_after_100us": int((st > 100).sum()),
     }
+    if pend.any():
+        # phase 2 of a split: do pending-restoration records share a SIMD while other SIMDs hold none?  (all SIMDs of
+        # the device: 256 CUs x 4)
+        per_simd_pend = np.bincount(inv, weights=pend.astype(float)).astype(int)
+        shared = int(per_simd_pend[per_simd_pend > 1].sum())
+        out["pending"] = {"records": int(pend.sum()), "sharing_a_simd_with_another": shared,
+                          "per_simd_pending_max": int(per_simd_pend.max()),
+                          "simds_without_pending": int(1024 - (per_simd_pend > 0).sum()),
+                          "pending_start_q_us": q(st[pend]), "pending_end_q_us": q(en[pend]),
+                          "pending_us_per_iter_q": q((dur / np.maximum(its, 1))[pend])}
     return out
 
 
