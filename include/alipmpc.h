@@ -284,6 +284,48 @@ int alipmpc_closed_loop_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc,
 int alipmpc_nominal_gait_batch(void* handle, int64_t B, double vx_max, const double* x, const int8_t* leg,
                                const double* vel_des_in, double* vel_des, double* foot, void* hip_stream);
 
+/*
+ * Generate B Monte-Carlo scenes on the device: instances g = first_index .. first_index + B - 1 of the sweep
+ * (seed, fields, n_cir, n_elp, max_candidates).  Every output row is a pure function of those and g — never of B
+ * or of the call that produced it — so a rank generates exactly its shard and a sweep is never scattered.  The
+ * distribution is the reference's random obstacle fields (rand_obs.py:31-72: random_circle / random_obs, inflated by
+ * safe_dis = 0.4 as main_sim_mpc.py:11,14 does) and the initial states of alipmpc/scenes.py; the function itself and
+ * its stream have no reference counterpart.  alipmpc/scenes.py: make_batch_counter restates the stream on the host.
+ *
+ * The stream.  U(id, stream, ctr) in [0, 1) is splitmix64 of a counter: key = (((id * 4 + stream) << 20) | ctr) + 1,
+ * z = seed + 0x9E3779B97F4A7C15 * key, z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9, z = (z ^ z >> 27) * 0x94D049BB133111EB,
+ * z ^= z >> 31, U = (z >> 11) * 2^-53; id < 2^40, ctr < 2^20, stream 0 = field placement, 1 = ellipse shapes, 2 =
+ * instance state.  r2(v) = rint(v * 100) / 100 (np.round(v, 2)).  All arithmetic is fp64, every operation rounded on
+ * its own, left to right as written (no fused multiply-add).
+ *   Field of instance g: id = g % fields (fields == 0: id = g).  placed = [(10, 10, 0.3), (0, 0, 1.0)], spacing = 0.8,
+ *   tries = 0.  Candidate c = 0, 1, ...: x = r2(8.5 U(ctr 3c)), y = r2(8.5 U(3c + 1)), r = r2(0.65 U(3c + 2) + 0.35),
+ *   accepted when (x-cx)*(x-cx) + (y-cy)*(y-cy) - t*t >= 0 with t = (r + cr) + 2*spacing for every placed (cx, cy, cr);
+ *   accept: append, tries = 0; reject: tries += 1, and tries > 2000: spacing *= 0.5, tries = 0.  Stops at n_cir + n_elp
+ *   obstacles or after max_candidates candidates (0 = the default 2^18, also the limit; the field then holds fewer
+ *   obstacles and nc / ne say how many).  The two seed circles are dropped.
+ *   Mix fields (n_elp > 0; needs n_cir = ceil(tot / 2), n_elp = floor(tot / 2)): obstacle i in placement order is circle
+ *   slot i / 2 (i even) or ellipse slot j = (i - 1) / 2 (i odd) with a = r, b = r2((a / 2) U(stream 1, ctr 2j) + a / 2),
+ *   phi = r2(floor(181 U(stream 1, ctr 2j + 1)) * (pi / 180)).  Inflation: circle r + 0.4, ellipse a + 0.4, b + 0.4.
+ *   Slots past the count are zero.
+ *   State (stream 2, id = g): pair i = 0, 1, ...: px = 10 U(ctr 2i), py = 10 U(2i + 1), accepted when
+ *   (px-10)*(px-10) + (py-10)*(py-10) > 0.25 and dx*dx + dy*dy >= R*R for every inflated obstacle (R = r + 0.2 for a
+ *   circle, max(a, b) + 0.2 for an ellipse); after 1024 rejected pairs the last one is used.  leg = U(4096) < 0.5 ? -1
+ *   : +1, noise = 0.2 sqrt(-2 log(1 - U(4097))) cos(2 pi U(4098)), vbx = 0.45 + 0.3 U(4099), vby = -leg (0.17 + 0.16
+ *   U(4100)), th = atan2(10 - py, 10 - px) + noise, x0 = [px, py, cos(th) vbx - sin(th) vby, sin(th) vbx + cos(th) vby,
+ *   th], goal = (10, 10), u0 = [x0] * N.  (x0[2:5] pass through the device's log / sqrt / cos / sin / atan2: equal to the
+ *   host restatement to a few ulp, not bit for bit; everything else is.)
+ * Outputs, shaped as alipmpc_solve_batch's inputs for the handle's N, nc_max, ne_max (any may be NULL; elp / ne are
+ * ignored when ne_max == 0): x0 B x 5, goal B x 2, leg B, cir B x nc_max x 3, nc B, elp B x ne_max x 5, ne B, u0 B x 5N.
+ * Host pointers with hip_stream == NULL (staged, synchronous); device pointers otherwise: one kernel launch on that
+ * stream (one wavefront per instance), no host synchronisation, no device allocation.
+ * ALIPMPC_EINVAL: B < 0, n_cir > nc_max, n_elp > ne_max, a broken mix rule, fields < 0, max_candidates outside
+ * [0, 2^18], first_index < 0, first_index + B > 2^40.  LIP variants only (DD: ALIPMPC_EUNSUPPORTED).
+ */
+int alipmpc_scenes_batch(void* handle, int64_t B, uint64_t seed, int64_t first_index,
+                         int32_t n_cir, int32_t n_elp, int64_t fields, int32_t max_candidates,
+                         double* x0, double* goal, int8_t* leg, double* cir, int32_t* nc,
+                         double* elp, int32_t* ne, double* u0, void* hip_stream);
+
 /* Rows per planned step of alipmpc_trace_batch: 1 + len(np.arange(0, dt + 0.01, 0.01)) (42 at dt = 0.4);
  * 0 for the DD variant. */
 int32_t alipmpc_trace_len(const alipmpc_cfg* cfg);

@@ -46,7 +46,7 @@ EXPORTS = ("alipmpc_default_cfg", "alipmpc_rows_per_step", "alipmpc_num_vars", "
            "alipmpc_solve_batch", "alipmpc_eval_batch", "alipmpc_rollout_batch", "alipmpc_closed_loop_batch",
            "alipmpc_trace_len",
            "alipmpc_trace_batch", "alipmpc_nominal_gait_batch", "alipmpc_solve_slots", "alipmpc_solve_launches", "alipmpc_lane_handoffs", "alipmpc_solve_program", "alipmpc_last_kernel_ms",
-           "alipmpc_build_id",
+           "alipmpc_build_id", "alipmpc_scenes_batch",
            "alipmpc_last_error", "alipmpc_destroy")
 
 _lib = None
@@ -116,6 +116,10 @@ def load(build_if_missing=True):
     if hasattr(L, "alipmpc_build_id"):
         L.alipmpc_build_id.argtypes = []
         L.alipmpc_build_id.restype = ctypes.c_char_p
+    if hasattr(L, "alipmpc_scenes_batch"):   # (absent from older dev builds used for A/B timing)
+        L.alipmpc_scenes_batch.argtypes = [P, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32,
+                                           ctypes.c_int32, ctypes.c_int64, ctypes.c_int32] + [P] * 9
+        L.alipmpc_scenes_batch.restype = ctypes.c_int
     L.alipmpc_last_kernel_ms.argtypes = [P]
     L.alipmpc_last_kernel_ms.restype = ctypes.c_double
     L.alipmpc_last_error.argtypes = [P]
@@ -364,7 +368,39 @@ class Solver:
         self._check(rc, "alipmpc_trace_batch")
         return out
 
+    def scenes(self, B, seed=0, first=0, n_cir=None, n_elp=0, fields=0, max_candidates=0):
+        """Monte-Carlo scenes first .. first + B - 1 of the counter-based stream (alipmpc_scenes_batch), generated
+        on the device: the dict of scenes.make_batch (elp / ne None without ellipse slots).  n_cir defaults to the
+        handle's nc_max; fields > 0 shares that many obstacle fields (instance g uses field g % fields)."""
+        cfg, B = self.cfg, int(B)
+        n_cir = cfg.nc_max if n_cir is None else n_cir
+        Bn = max(B, 0)
+        out = dict(x0=np.zeros((Bn, 5)), goal=np.zeros((Bn, 2)), leg=np.zeros(Bn, np.int8),
+                   cir=np.zeros((Bn, cfg.nc_max, 3)), nc=np.zeros(Bn, np.int32),
+                   elp=np.zeros((Bn, cfg.ne_max, 5)) if cfg.ne_max else None,
+                   ne=np.zeros(Bn, np.int32) if cfg.ne_max else None, u0=np.zeros((Bn, 5 * cfg.N)))
+        rc = self._L.alipmpc_scenes_batch(self._h, B, int(seed), int(first), int(n_cir), int(n_elp), int(fields),
+                                          int(max_candidates), _ptr(out["x0"]), _ptr(out["goal"]), _ptr(out["leg"]),
+                                          _ptr(out["cir"]), _ptr(out["nc"]), _ptr(out["elp"]), _ptr(out["ne"]),
+                                          _ptr(out["u0"]), None)
+        self._check(rc, "alipmpc_scenes_batch")
+        return out
+
     # ---------------------------------------------------------------- device (torch) calls
+    def scenes_device(self, out, seed=0, first=0, n_cir=None, n_elp=0, fields=0, max_candidates=0, stream=None):
+        """Asynchronous scene generation into device tensors: out holds any of x0 (B,5), goal (B,2), leg (int8),
+        cir (B,nc_max,3), nc (int32), elp (B,ne_max,5), ne (int32), u0 (B,5N) — the keys of solve_device's inp, so
+        the solve reads what this wrote, on the same stream, with no copy.  B is the leading size of out's tensors."""
+        import torch
+        st = stream if stream is not None else torch.cuda.current_stream()
+        B = next(v for v in out.values() if v is not None).shape[0]
+        n_cir = self.cfg.nc_max if n_cir is None else n_cir
+        rc = self._L.alipmpc_scenes_batch(
+            self._h, B, int(seed), int(first), int(n_cir), int(n_elp), int(fields), int(max_candidates),
+            _ptr(out.get("x0")), _ptr(out.get("goal")), _ptr(out.get("leg")), _ptr(out.get("cir")),
+            _ptr(out.get("nc")), _ptr(out.get("elp")), _ptr(out.get("ne")), _ptr(out.get("u0")), _stream_arg(st))
+        self._check(rc, "alipmpc_scenes_batch")
+
     def rollout_device(self, inp, out, steps, stream=None):
         """Asynchronous rollout on device tensors: inp as solve_device, out dict with any of foot (B,S,3),
         x (B,S+1,sdim), status (B,S), iters (B,S), steps_to_goal (B,), u (B,S,n)."""

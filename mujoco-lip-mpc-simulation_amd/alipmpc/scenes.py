@@ -205,3 +205,156 @@ def make_batch_vec(B, seed=0, n_cir=5, n_elp=0, N=3, fields=None, max_rounds=400
                 elp=np.ascontiguousarray(elp) if n_elp else None,
                 ne=np.full(B, elp.shape[1], np.int32) if n_elp else None,
                 u0=np.tile(x0, (1, N)))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Counter-based stream (include/alipmpc.h: alipmpc_scenes_batch; csrc/scenes.inc is the device form).
+# Every row is a pure function of (seed, global index, fields, n_cir, n_elp, max_candidates), so any index range
+# can be generated on its own.  This is the host restatement: the yardstick of the device kernel and a CPU
+# fallback for tools, not a fast path.  Same distribution as make_batch, a different stream.
+# ---------------------------------------------------------------------------------------------------------------
+MAX_CANDIDATES = 1 << 18      # default and limit of max_candidates
+MAX_TRIES = 2000              # consecutive rejections before the spacing is halved
+STATE_PAIRS = 1024            # initial-state pairs tried before the last one is taken
+STREAM_FIELD, STREAM_SHAPE, STREAM_STATE = 0, 1, 2
+CTR_LEG = 4096                # stream 2: leg, heading noise (2 draws), vbx, vby follow the position pairs
+_M64 = (1 << 64) - 1
+
+
+def counter_uniform(seed, id, stream, ctr):
+    """U(seed, id, stream, ctr) in [0, 1): splitmix64 of the counter (id < 2^40, stream < 4, ctr < 2^20)."""
+    key = ((((int(id) * 4 + int(stream)) << 20) | int(ctr)) + 1) & _M64
+    z = (int(seed) + 0x9E3779B97F4A7C15 * key) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    z ^= z >> 31
+    return (z >> 11) * 2.0 ** -53
+
+
+def counter_uniforms(seed, id, stream, ctr):
+    """counter_uniform for an array of counters (uint64 arithmetic wraps as the scalar form masks)."""
+    ctr = np.asarray(ctr, np.uint64)
+    base = np.uint64((int(id) * 4 + int(stream)) << 20)
+    with np.errstate(over="ignore"):
+        key = (base | ctr) + np.uint64(1)
+        z = np.uint64(int(seed) & _M64) + np.uint64(0x9E3779B97F4A7C15) * key
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    return (z >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+
+
+def _r2(v):
+    return np.rint(v * 100) / 100          # np.round(v, 2)
+
+
+def counter_field(seed, fid, tot, max_candidates=MAX_CANDIDATES):
+    """Placement of field `fid`: the sequential rejection loop of random_circles on stream 0.  Returns the placed
+    obstacles [x, y, r] (fewer than tot when max_candidates ran out), seed circles dropped."""
+    placed = [(10.0, 10.0, 0.3), (0.0, 0.0, 1.0)]
+    spacing, tries, c, block = 0.8, 0, 0, 32
+    while len(placed) < tot + 2 and c < max_candidates:
+        n = min(block, max_candidates - c)
+        u = counter_uniforms(seed, fid, STREAM_FIELD, np.arange(3 * c, 3 * (c + n)))
+        xs, ys = _r2(8.5 * u[0::3]).tolist(), _r2(8.5 * u[1::3]).tolist()
+        rs = _r2(0.65 * u[2::3] + 0.35).tolist()
+        for x, y, r in zip(xs, ys, rs):
+            c += 1
+            ok = True
+            for cx, cy, cr in placed:
+                t = (r + cr) + 2 * spacing
+                if not ((x - cx) * (x - cx) + (y - cy) * (y - cy) - t * t >= 0):
+                    ok = False
+                    break
+            if ok:
+                placed.append((x, y, r))
+                tries = 0
+                if len(placed) == tot + 2:
+                    break
+            else:
+                tries += 1
+                if tries > MAX_TRIES:
+                    spacing *= 0.5
+                    tries = 0
+        block = min(4 * block, 4096)
+    return np.array(placed[2:], np.float64).reshape(-1, 3)
+
+
+def counter_scene(seed, fid, n_cir, n_elp, max_candidates=MAX_CANDIDATES):
+    """Inflated obstacles of field `fid`: (cir (nc, 3), elp (ne, 5))."""
+    obs = counter_field(seed, fid, n_cir + n_elp, max_candidates)
+    if n_elp > 0:
+        cir = obs[0::2].copy()
+        odd = obs[1::2]
+        j = np.arange(len(odd))
+        a = odd[:, 2]
+        b = _r2((a / 2) * counter_uniforms(seed, fid, STREAM_SHAPE, 2 * j) + a / 2)
+        phi = _r2(np.floor(181 * counter_uniforms(seed, fid, STREAM_SHAPE, 2 * j + 1)) * (np.pi / 180))
+        elp = np.stack([odd[:, 0], odd[:, 1], a + SAFE_DIS, b + SAFE_DIS, phi], axis=1)
+    else:
+        cir, elp = obs.copy(), np.zeros((0, 5))
+    cir[:, 2] = cir[:, 2] + SAFE_DIS
+    return cir, elp
+
+
+def counter_state(seed, g, cir, elp):
+    """Initial state and leg of instance g (stream 2) among the inflated obstacles cir / elp."""
+    ox = np.concatenate([cir[:, 0], elp[:, 0]])
+    oy = np.concatenate([cir[:, 1], elp[:, 1]])
+    R = np.concatenate([cir[:, 2], np.maximum(elp[:, 2], elp[:, 3])]) + 0.2
+    RR = R * R
+    px = py = 0.0
+    for i0 in range(0, STATE_PAIRS, 64):
+        u = counter_uniforms(seed, g, STREAM_STATE, np.arange(2 * i0, 2 * (i0 + 64)))
+        qx, qy = 10 * u[0::2], 10 * u[1::2]
+        ok = (qx - 10) * (qx - 10) + (qy - 10) * (qy - 10) > 0.25
+        dx, dy = qx[:, None] - ox[None, :], qy[:, None] - oy[None, :]
+        ok &= np.all(dx * dx + dy * dy >= RR[None, :], axis=1)
+        k = int(np.argmax(ok)) if ok.any() else 63
+        px, py = float(qx[k]), float(qy[k])
+        if ok.any():
+            break
+    leg = -1 if counter_uniform(seed, g, STREAM_STATE, CTR_LEG) < 0.5 else 1
+    noise = 0.2 * np.sqrt(-2 * np.log(1 - counter_uniform(seed, g, STREAM_STATE, CTR_LEG + 1))) * \
+        np.cos(2 * np.pi * counter_uniform(seed, g, STREAM_STATE, CTR_LEG + 2))
+    vbx = 0.45 + 0.3 * counter_uniform(seed, g, STREAM_STATE, CTR_LEG + 3)
+    vby = -leg * (0.17 + 0.16 * counter_uniform(seed, g, STREAM_STATE, CTR_LEG + 4))
+    th = np.arctan2(10 - py, 10 - px) + noise
+    c, s = np.cos(th), np.sin(th)
+    return np.array([px, py, c * vbx - s * vby, s * vbx + c * vby, th]), leg
+
+
+def make_batch_counter(B, seed=0, first=0, n_cir=5, n_elp=0, N=3, nc_max=None, ne_max=None, fields=0,
+                       max_candidates=0):
+    """Instances first .. first + B - 1 of the counter-based stream: the dict of make_batch.  fields > 0: instance g
+    uses obstacle field g % fields (0: its own).  max_candidates: candidates per field (0: 2^18); a field that runs
+    out holds fewer obstacles (nc / ne say how many, the other slots are zero)."""
+    nc_max = n_cir if nc_max is None else nc_max
+    ne_max = n_elp if ne_max is None else ne_max
+    maxc = max_candidates or MAX_CANDIDATES
+    tot = n_cir + n_elp
+    if B < 0 or first < 0 or first + B > 1 << 40 or fields < 0 or not 0 < maxc <= MAX_CANDIDATES:
+        raise ValueError("make_batch_counter: index range, fields or max_candidates out of range")
+    if not (0 <= n_cir <= nc_max and 0 <= n_elp <= ne_max) or (n_elp > 0 and (n_cir, n_elp) != ((tot + 1) // 2, tot // 2)):
+        raise ValueError("make_batch_counter: n_cir / n_elp do not fit the slots or the mix rule")
+    x0 = np.zeros((B, 5))
+    leg = np.zeros(B, np.int8)
+    cir = np.zeros((B, nc_max, 3))
+    elp = np.zeros((B, ne_max, 5))
+    nc = np.zeros(B, np.int32)
+    ne = np.zeros(B, np.int32)
+    cache = {}
+    for b in range(B):
+        g = first + b
+        fid = g % fields if fields else g
+        if fid not in cache:
+            cache[fid] = counter_scene(seed, fid, n_cir, n_elp, maxc)
+        cs, es = cache[fid]
+        if not fields:
+            del cache[fid]
+        nc[b], ne[b] = len(cs), len(es)
+        cir[b, :len(cs)] = cs
+        elp[b, :len(es)] = es
+        x0[b], leg[b] = counter_state(seed, g, cs, es)
+    return dict(x0=x0, goal=np.tile(np.array(GOAL), (B, 1)), leg=leg, cir=cir, nc=nc,
+                elp=elp if ne_max else None, ne=ne if ne_max else None, u0=np.tile(x0, (1, N)))

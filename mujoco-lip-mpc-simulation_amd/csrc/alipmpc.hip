@@ -5180,6 +5180,8 @@ hipError_t launch_sweep(int nc, bool fen, const KP& P, hipStream_t st)
 }  // namespace alip
 
 #if ALIP_PART_HOST
+#include "scenes.inc"   // counter-based scene generator (alipmpc_scenes_batch)
+
 // ================================================================================================
 // host side: constants, handle, C ABI
 // ================================================================================================
@@ -6592,6 +6594,69 @@ int alipmpc_nominal_gait_batch(void* handle, int64_t B, double vx_max, const dou
     if (host) {
         if (vel_des) HIPCHK(h, hipMemcpyAsync(vel_des, Q.vout, Bz * 2 * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(h, hipMemcpyAsync(foot, Q.foot, Bz * 2 * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipStreamSynchronize(st));
+    }
+    return ALIPMPC_OK;
+}
+
+int alipmpc_scenes_batch(void* handle, int64_t B, uint64_t seed, int64_t first_index, int32_t n_cir, int32_t n_elp,
+                         int64_t fields, int32_t max_candidates, double* x0, double* goal, int8_t* leg, double* cir,
+                         int32_t* nc, double* elp, int32_t* ne, double* u0, void* hip_stream)
+{
+    Handle* h = (Handle*)handle;
+    if (!h) return ALIPMPC_EINVAL;
+    const alipmpc_cfg& cf = h->cfg;
+    if (cf.variant == ALIPMPC_VARIANT_DD) return fail(h, ALIPMPC_EUNSUPPORTED, "scenes: LIP variants only");
+    if (B < 0) return fail(h, ALIPMPC_EINVAL, "B < 0");
+    if (n_cir < 0 || n_cir > cf.nc_max) return fail(h, ALIPMPC_EINVAL, "scenes: n_cir outside [0, nc_max]");
+    if (n_elp < 0 || n_elp > cf.ne_max) return fail(h, ALIPMPC_EINVAL, "scenes: n_elp outside [0, ne_max]");
+    if (n_cir + n_elp > ALIPMPC_MAX_OBS) return fail(h, ALIPMPC_EINVAL, "scenes: n_cir + n_elp > ALIPMPC_MAX_OBS");
+    if (n_elp > 0 && n_cir - n_elp != 0 && n_cir - n_elp != 1)
+        return fail(h, ALIPMPC_EINVAL, "scenes: a mix field needs n_cir = ceil(tot / 2), n_elp = floor(tot / 2)");
+    if (fields < 0) return fail(h, ALIPMPC_EINVAL, "scenes: fields < 0");
+    if (max_candidates < 0 || max_candidates > SC_MAX_CAND)
+        return fail(h, ALIPMPC_EINVAL, "scenes: max_candidates outside [0, 2^18]");
+    const int64_t id_end = (int64_t)1 << 40;
+    if (first_index < 0 || first_index > id_end || B > id_end - first_index)
+        return fail(h, ALIPMPC_EINVAL, "scenes: global indices outside [0, 2^40)");
+    if (B == 0) return ALIPMPC_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t Bz = (size_t)B, ncm = (size_t)cf.nc_max, nem = (size_t)cf.ne_max, nu = (size_t)5 * h->N;
+    ScP S;
+    std::memset(&S, 0, sizeof(S));
+    S.B = B; S.first = first_index; S.fields = fields; S.seed = seed;
+    S.n_cir = n_cir; S.n_elp = n_elp; S.nc_max = cf.nc_max; S.ne_max = cf.ne_max; S.N = h->N;
+    S.max_cand = max_candidates ? max_candidates : SC_MAX_CAND;
+    hipStream_t st = stream_of(h, hip_stream);
+    const bool host = hip_stream == nullptr;
+    if (!nem) elp = nullptr, ne = nullptr;   // no ellipse slots: ignored
+    if (host) {
+        if (int rc = ensure_stage(h, Bz * 8 * (5 + 2 + 3 * ncm + 5 * nem + nu) + Bz * (1 + 4 + 4) + 8 * 256)) return rc;
+        Carver cv{(char*)h->stage};
+        S.x0 = x0 ? cv.take<double>(Bz * 5) : nullptr;
+        S.goal = goal ? cv.take<double>(Bz * 2) : nullptr;
+        S.cir = cir ? cv.take<double>(Bz * 3 * ncm) : nullptr;
+        S.elp = elp ? cv.take<double>(Bz * 5 * nem) : nullptr;
+        S.u0 = u0 ? cv.take<double>(Bz * nu) : nullptr;
+        S.nc = nc ? cv.take<int32_t>(Bz) : nullptr;
+        S.ne = ne ? cv.take<int32_t>(Bz) : nullptr;
+        S.leg = leg ? cv.take<int8_t>(Bz) : nullptr;
+    } else {
+        S.x0 = x0; S.goal = goal; S.leg = leg; S.cir = cir; S.nc = nc; S.elp = elp; S.ne = ne; S.u0 = u0;
+    }
+    // one wavefront per instance; a bounded grid strides over larger batches
+    const long long blocks = std::min<long long>((B + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 1ll << 20);
+    hipLaunchKernelGGL(scenes_kernel, dim3((unsigned)blocks), dim3(WAVE * WAVES_PER_BLOCK), 0, st, S);
+    HIPCHK(h, hipGetLastError());
+    if (host) {
+        if (x0) HIPCHK(h, hipMemcpyAsync(x0, S.x0, Bz * 5 * 8, hipMemcpyDeviceToHost, st));
+        if (goal) HIPCHK(h, hipMemcpyAsync(goal, S.goal, Bz * 2 * 8, hipMemcpyDeviceToHost, st));
+        if (cir && ncm) HIPCHK(h, hipMemcpyAsync(cir, S.cir, Bz * 3 * ncm * 8, hipMemcpyDeviceToHost, st));
+        if (elp) HIPCHK(h, hipMemcpyAsync(elp, S.elp, Bz * 5 * nem * 8, hipMemcpyDeviceToHost, st));
+        if (u0) HIPCHK(h, hipMemcpyAsync(u0, S.u0, Bz * nu * 8, hipMemcpyDeviceToHost, st));
+        if (nc) HIPCHK(h, hipMemcpyAsync(nc, S.nc, Bz * 4, hipMemcpyDeviceToHost, st));
+        if (ne) HIPCHK(h, hipMemcpyAsync(ne, S.ne, Bz * 4, hipMemcpyDeviceToHost, st));
+        if (leg) HIPCHK(h, hipMemcpyAsync(leg, S.leg, Bz, hipMemcpyDeviceToHost, st));
         HIPCHK(h, hipStreamSynchronize(st));
     }
     return ALIPMPC_OK;
