@@ -274,6 +274,40 @@ int alipmpc_closed_loop_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc,
                               double* foot_traj, double* x_traj, double* hd_traj, int32_t* status_traj,
                               int32_t* iters_traj, int32_t* steps_to_goal, double* action_traj, void* hip_stream);
 
+/*
+ * The closed loop of alipmpc_closed_loop_batch — same arguments, same outputs, bit for bit — that also writes the
+ * imitation-learning rows the reference's logger records per MPC call (data_procs/logger_iml.py:377-401 X and
+ * y_mpc, :416-428 y_act; sup_learn/X_data.csv, y_mpc_data.csv, y_act_data.csv).  Every tick (b, s, i) whose solve
+ * ran (status != ALIPMPC_ROLLOUT_DONE) gives one row; rows are episode-major, then step, then tick, compacted on the
+ * device: episode b owns rows row_start[b] .. row_start[b + 1] - 1 (f_cyc per step it entered), row_start[B] is
+ * the total.
+ *   X          3 nc_max + 5 ne_max + 11 columns: circle slots [cx, cy, r - safe_dis], ellipse slots [cx, cy,
+ *              a - safe_dis, b - safe_dis, phi] as passed (slots past nc / ne zero; safe_dis = 0.4 gives back the
+ *              raw radii logger_iml.py:67 records), then the plant's CoM position (2), velocity (2) and heading
+ *              before the tick, the stance foot (2), the goal (2), leg_ind (the plant's), rest_t = T - i (T / f_cyc);
+ *   y_mpc      8: p_list[0][0:2] of the tick's solve, 0, hd_input_pr + hd_input_cos (robot frame, as action_traj
+ *              [..., 3] uses it), x_nex[0:2], v_des_map (2) as it stood before this tick's update;
+ *   y_act      8, the same for all f_cyc rows of a step: stance foot after the touchdown (2), 0, plant heading,
+ *              CoM position (2) and velocity (2) at the touchdown;
+ *   row_status int32, the tick's solve status.
+ * first_index: the kick stream's episode id is first_index + b, so a shard of a sweep gives the rows the whole
+ * sweep gives (0: alipmpc_closed_loop_batch's stream); first_index < 0 or first_index + B > 2^32: ALIPMPC_EINVAL,
+ * as are a negative or non-finite safe_dis and max_rows < 0.  max_rows is the capacity of X / y_mpc / y_act /
+ * row_status in rows: rows at positions >= max_rows are not written, row_start (B + 1 entries) is complete
+ * whatever max_rows is — compare row_start[B] with max_rows; B * S * f_cyc always suffices.  Any of the five may be
+ * NULL (row_start alone sizes a second call).  Row contents depend only on the episode's inputs, seed and
+ * first_index + b: not on B, the episode groups or the pointer mode.  Device-pointer calls never synchronise with
+ * the host.  The rows cost a B x S x f_cyc x 88-byte staging area in the handle's workspace (ALIPMPC_EHIP with the
+ * size in the message if it cannot be allocated) and two kernels after the loop.
+ */
+int alipmpc_closed_loop_dataset_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc, double kick, uint64_t seed,
+                                      const double* x0, const double* foot0, const double* goal, const int8_t* leg,
+                                      const double* cir, const int32_t* nc, const double* elp, const int32_t* ne,
+                                      double* foot_traj, double* x_traj, double* hd_traj, int32_t* status_traj,
+                                      int32_t* iters_traj, int32_t* steps_to_goal, double* action_traj,
+                                      int64_t first_index, double safe_dis, int64_t max_rows, double* X, double* y_mpc,
+                                      double* y_act, int32_t* row_status, int64_t* row_start, void* hip_stream);
+
 /* Nominal gait of a batch (replaces MPCCBF.alip_des_vel / cal_foot_with_veldes, MPC_LIP_modi.py:181-194, used by
  * the driver at main_sim_mpc.py:54 and the ALIP-only loggers):
  *   vel_des = alip_des_vel(vx_max, leg_ind) = [sigma vx_max T / 2, 0.5 (-0.5 leg_ind step_gap) beta sinh(beta T) /

@@ -3,6 +3,7 @@
   Solver       one libalipmpc.so handle: batched solve / eval on host or device buffers
   default_cfg  the reference's constants per variant (modi / sig_step / dd)
   planner      MPCCBF drop-in (reference MPC_LIP_modi.MPCCBF signatures) + solve_batch
+  dataset      imitation-learning rows (X, y_mpc, y_act) of Solver.closed_loop_dataset: check_rows, CSV / npz writers
 """
 from ._lib import (Cfg, Solver, default_cfg, load, lib_path, build_id, num_vars, rows_per_step, trace_len, EXPORTS, STATUS_NAMES,
                    VARIANT_MODI, VARIANT_SIG_STEP, VARIANT_DD, PREC_FP64, PREC_FP32, PROGRAM_WAVE, PROGRAM_LANE,

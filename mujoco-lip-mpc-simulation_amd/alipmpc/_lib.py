@@ -44,7 +44,7 @@ class Cfg(ctypes.Structure):
 
 EXPORTS = ("alipmpc_default_cfg", "alipmpc_rows_per_step", "alipmpc_num_vars", "alipmpc_create",
            "alipmpc_solve_batch", "alipmpc_eval_batch", "alipmpc_rollout_batch", "alipmpc_closed_loop_batch",
-           "alipmpc_trace_len",
+           "alipmpc_closed_loop_dataset_batch", "alipmpc_trace_len",
            "alipmpc_trace_batch", "alipmpc_nominal_gait_batch", "alipmpc_solve_slots", "alipmpc_solve_launches", "alipmpc_lane_handoffs", "alipmpc_solve_program", "alipmpc_last_kernel_ms",
            "alipmpc_build_id", "alipmpc_scenes_batch",
            "alipmpc_last_error", "alipmpc_destroy")
@@ -93,6 +93,11 @@ def load(build_if_missing=True):
     L.alipmpc_closed_loop_batch.argtypes = [P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
                                             ctypes.c_uint64] + [P] * 16
     L.alipmpc_closed_loop_batch.restype = ctypes.c_int
+    if hasattr(L, "alipmpc_closed_loop_dataset_batch"):   # (absent from older dev builds used for A/B timing)
+        L.alipmpc_closed_loop_dataset_batch.argtypes = [P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                        ctypes.c_double, ctypes.c_uint64] + [P] * 15 + \
+                                                       [ctypes.c_int64, ctypes.c_double, ctypes.c_int64] + [P] * 6
+        L.alipmpc_closed_loop_dataset_batch.restype = ctypes.c_int
     L.alipmpc_trace_len.argtypes = [ctypes.POINTER(Cfg)]
     L.alipmpc_trace_len.restype = ctypes.c_int32
     L.alipmpc_trace_batch.argtypes = [P, ctypes.c_int64, P, P, P, P]
@@ -344,6 +349,61 @@ class Solver:
             _ptr(out.get("status")), _ptr(out.get("iters")), _ptr(out.get("steps_to_goal")), _ptr(out.get("action")),
             _stream_arg(st))
         self._check(rc, "alipmpc_closed_loop_batch")
+
+    def x_cols(self):
+        """Columns of the dataset's X: 3 nc_max + 5 ne_max + 11 (include/alipmpc.h)."""
+        return 3 * self.cfg.nc_max + 5 * self.cfg.ne_max + 11
+
+    def closed_loop_dataset(self, x0, foot0, goal, leg, cir, nc, elp=None, ne=None, steps=8, f_cyc=8, kick=0.0,
+                            seed=0, first=0, safe_dis=0.4, max_rows=None):
+        """closed_loop that also returns the imitation-learning rows of every tick that ran
+        (alipmpc_closed_loop_dataset_batch): the dict of closed_loop plus X (R, 3 nc_max + 5 ne_max + 11), y_mpc (R, 8),
+        y_act (R, 8), row_status (R,), row_start (B + 1,) — episode b owns rows row_start[b] .. row_start[b + 1] - 1 —
+        trimmed to the total R = row_start[B].  `first`: global index of episode 0 (the kick stream's episode id).
+        max_rows (default B * steps * f_cyc, which always suffices) caps the rows written; rows past it are lost and
+        R = min(row_start[B], max_rows)."""
+        B, x0, goal, leg, cir, nc, elp, ne = self._inputs(x0, goal, leg, cir, nc, elp, ne)
+        foot0 = np.ascontiguousarray(foot0, np.float64).reshape(B, 2)
+        S, F = int(steps), int(f_cyc)
+        cap = B * S * F if max_rows is None else int(max_rows)
+        n = max(cap, 0)
+        out = dict(foot=np.zeros((B, S, 3)), x=np.zeros((B, S + 1, 5)), hd=np.zeros((B, S, 2)),
+                   status=np.zeros((B, S, F), np.int32), iters=np.zeros((B, S, F), np.int32),
+                   steps_to_goal=np.zeros(B, np.int32), action=np.zeros((B, S, F, 8)),
+                   X=np.zeros((n, self.x_cols())), y_mpc=np.zeros((n, 8)), y_act=np.zeros((n, 8)),
+                   row_status=np.zeros(n, np.int32), row_start=np.zeros(B + 1, np.int64))
+        rc = self._L.alipmpc_closed_loop_dataset_batch(
+            self._h, B, S, F, float(kick), int(seed), _ptr(x0), _ptr(foot0), _ptr(goal), _ptr(leg), _ptr(cir),
+            _ptr(nc), _ptr(elp), _ptr(ne), _ptr(out["foot"]), _ptr(out["x"]), _ptr(out["hd"]), _ptr(out["status"]),
+            _ptr(out["iters"]), _ptr(out["steps_to_goal"]), _ptr(out["action"]), int(first), float(safe_dis), cap,
+            _ptr(out["X"]), _ptr(out["y_mpc"]), _ptr(out["y_act"]), _ptr(out["row_status"]), _ptr(out["row_start"]),
+            None)
+        self._check(rc, "alipmpc_closed_loop_dataset_batch")
+        R = min(int(out["row_start"][B]), n)
+        for k in ("X", "y_mpc", "y_act", "row_status"):
+            out[k] = out[k][:R]
+        return out
+
+    def closed_loop_dataset_device(self, inp, out, steps, f_cyc=8, kick=0.0, seed=0, first=0, safe_dis=0.4,
+                                   max_rows=None, stream=None):
+        """Asynchronous closed loop with rows on device tensors: inp / out as closed_loop_device, out also with any
+        of X (max_rows, 3 nc_max + 5 ne_max + 11), y_mpc (max_rows, 8), y_act (max_rows, 8), row_status (max_rows,)
+        int32, row_start (B + 1,) int64.  max_rows defaults to the leading size of the first row tensor given.  Rows
+        at positions >= max_rows are not written; the caller reads row_start[B] once the stream is done."""
+        import torch
+        st = stream if stream is not None else torch.cuda.current_stream()
+        B = inp["x0"].shape[0]
+        if max_rows is None:
+            rows = [out[k] for k in ("X", "y_mpc", "y_act", "row_status") if out.get(k) is not None]
+            max_rows = min(t.shape[0] for t in rows) if rows else 0
+        rc = self._L.alipmpc_closed_loop_dataset_batch(
+            self._h, B, int(steps), int(f_cyc), float(kick), int(seed), _ptr(inp["x0"]), _ptr(inp["foot0"]),
+            _ptr(inp["goal"]), _ptr(inp["leg"]), _ptr(inp["cir"]), _ptr(inp["nc"]), _ptr(inp.get("elp")),
+            _ptr(inp.get("ne")), _ptr(out.get("foot")), _ptr(out.get("x")), _ptr(out.get("hd")),
+            _ptr(out.get("status")), _ptr(out.get("iters")), _ptr(out.get("steps_to_goal")), _ptr(out.get("action")),
+            int(first), float(safe_dis), int(max_rows), _ptr(out.get("X")), _ptr(out.get("y_mpc")),
+            _ptr(out.get("y_act")), _ptr(out.get("row_status")), _ptr(out.get("row_start")), _stream_arg(st))
+        self._check(rc, "alipmpc_closed_loop_dataset_batch")
 
     def nominal_gait(self, x, leg=None, vx_max=0.6, vel_des=None):
         """Nominal gait (alipmpc_nominal_gait_batch): returns (vel_des (B,2), foot (B,2)) — alip_des_vel(vx_max,

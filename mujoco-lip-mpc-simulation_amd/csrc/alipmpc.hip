@@ -4520,7 +4520,12 @@ struct CLP {
     double* vdes;           // B x 2 v_des_map (main_sim_mpc.py:54, 88, 112)
     double* pose0;          // B x 3 the initial pose: origin / heading of the Logger's robot-global frame
     double vdx, vdy0;       // alip_des_vel(0.6, leg_ind) = [vdx, -0.25 * 0.3 * leg_ind * vdy0]
+    // imitation-learning rows (alipmpc_closed_loop_dataset_batch, dataset.inc), all three NULL otherwise
+    double* ds_tick;        // B x S x f x DS_TICK: plant state (5), planned foothold (2), x_nex (2), v_des (2)
+    double* ds_step;        // B x S x DS_STEP: stance foot (2), heading input, leg_ind, touchdown state (5)
+    int32_t* ds_nst;        // B: steps entered (wanted for row_start alone too)
 };
+constexpr int DS_TICK = 11, DS_STEP = 9;
 
 // Logger.angle_A_minus_B (logger_mpc.py:169-175)
 __host__ __device__ inline double ang_diff(double A, double B)
@@ -4678,6 +4683,26 @@ __global__ __launch_bounds__(256) void cl_update_kernel(CLP C)
     }
     double* x = C.x + 5 * b;
     const double fx = C.pst[2 * b], fy = C.pst[2 * b + 1];
+    if (C.ds_tick) {
+        // what the reference's logger records of this tick (logger_iml.py:377-401): the plant before it moves, the
+        // planned foothold, x_nex and v_des_map before this tick's update
+        double* d = C.ds_tick + ti * DS_TICK;
+        for (int c = 0; c < 5; ++c) d[c] = x[c];
+        d[5] = C.foot[3 * b];
+        d[6] = C.foot[3 * b + 1];
+        d[7] = C.xs[5 * b];
+        d[8] = C.xs[5 * b + 1];
+        d[9] = C.vdes[2 * b];
+        d[10] = C.vdes[2 * b + 1];
+        if (C.i == 0) {
+            double* e = C.ds_step + ((size_t)b * C.S + C.s) * DS_STEP;
+            e[0] = fx;
+            e[1] = fy;
+            e[2] = hv[1] + (hv[2] - C.pose0[3 * b + 2]);   // hd_input_pr + hd_input_cos (robot frame)
+            e[3] = (double)C.leg[b];
+        }
+    }
+    if (C.ds_nst && C.i == 0) C.ds_nst[b] = C.s + 1;
     if (C.action_traj) {
         // gen_nex_foot_input (logger_mpc.py:318-360) + gen_tsc_control (:374-384): robot-global frame = the
         // map frame moved to the initial pose (pos/vel_map_glo_2_robo_glo, :134-150); the foot frame is the
@@ -4736,6 +4761,8 @@ __global__ __launch_bounds__(256) void cl_update_kernel(CLP C)
             for (int c = 0; c < 3; ++c) C.foot_traj[((size_t)b * C.S + C.s) * 3 + c] = C.foot[3 * b + c];
         if (C.x_traj)
             for (int c = 0; c < 5; ++c) C.x_traj[((size_t)b * (C.S + 1) + C.s + 1) * 5 + c] = xn[c];
+        if (C.ds_step)
+            for (int c = 0; c < 5; ++c) C.ds_step[((size_t)b * C.S + C.s) * DS_STEP + 4 + c] = xn[c];
         if (fl & 4) {
             fl &= (uint8_t)~1u;
             if (C.steps_to_goal) C.steps_to_goal[b] = C.s + 1;
@@ -4755,6 +4782,7 @@ __global__ __launch_bounds__(256) void cl_init_kernel(CLP C)
     // the initial heading in the map frame the plant and the MPC share here
     for (int k = 0; k < 3; ++k) C.mhd[3 * b + k] = C.x[5 * b + 4];
     if (C.steps_to_goal) C.steps_to_goal[b] = -1;
+    if (C.ds_nst) C.ds_nst[b] = 0;
     if (C.x_traj)
         for (int c = 0; c < 5; ++c) C.x_traj[(size_t)b * (C.S + 1) * 5 + c] = C.x[5 * b + c];
     if (C.vdes) {   // vel_des = alip_des_vel(0.6, leg_ind) (main_sim_mpc.py:54)
@@ -5181,6 +5209,7 @@ hipError_t launch_sweep(int nc, bool fen, const KP& P, hipStream_t st)
 
 #if ALIP_PART_HOST
 #include "scenes.inc"   // counter-based scene generator (alipmpc_scenes_batch)
+#include "dataset.inc"  // row scan / compaction of alipmpc_closed_loop_dataset_batch
 
 // ================================================================================================
 // host side: constants, handle, C ABI
@@ -6254,17 +6283,51 @@ int alipmpc_rollout_batch(void* handle, int64_t B, int32_t S, const double* x0, 
     return ALIPMPC_OK;
 }
 
-int alipmpc_closed_loop_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc, double kick, uint64_t seed,
-                              const double* x0, const double* foot0, const double* goal, const int8_t* leg,
-                              const double* cir, const int32_t* nc, const double* elp, const int32_t* ne,
-                              double* foot_traj, double* x_traj, double* hd_traj, int32_t* status_traj,
-                              int32_t* iters_traj, int32_t* steps_to_goal, double* action_traj, void* hip_stream)
+// the dataset end of alipmpc_closed_loop_dataset_batch (nullptr: alipmpc_closed_loop_batch)
+struct DsArgs {
+    int64_t first_index;
+    double safe_dis;
+    int64_t max_rows;
+    double *X, *y_mpc, *y_act;
+    int32_t* row_status;
+    int64_t* row_start;
+};
+
+// both closed-loop entry points.  Without ds the launches, grouping, workspace layout and results are those of
+// alipmpc_closed_loop_batch as it always was: everything the dataset adds is carved after the existing areas and
+// sits behind a test of ds or of a staging pointer.
+static int closed_loop_impl(Handle* h, int64_t B, int32_t S, int32_t f_cyc, double kick, uint64_t seed,
+                            const double* x0, const double* foot0, const double* goal, const int8_t* leg,
+                            const double* cir, const int32_t* nc, const double* elp, const int32_t* ne,
+                            double* foot_traj, double* x_traj, double* hd_traj, int32_t* status_traj,
+                            int32_t* iters_traj, int32_t* steps_to_goal, double* action_traj, void* hip_stream,
+                            const DsArgs* ds)
 {
-    Handle* h = (Handle*)handle;
     if (!h) return ALIPMPC_EINVAL;
     const alipmpc_cfg& cf = h->cfg;
     if (cf.variant == ALIPMPC_VARIANT_DD) return fail(h, ALIPMPC_EUNSUPPORTED, "closed loop: LIP variants only");
     if (B < 0 || S < 0 || f_cyc < 1 || !(kick >= 0)) return fail(h, ALIPMPC_EINVAL, "B, S < 0, f_cyc < 1 or kick < 0");
+    const int ncx = 3 * cf.nc_max + 5 * cf.ne_max + 11;   // columns of X
+    if (ds) {
+        if (ds->first_index < 0 || ds->first_index > (int64_t)1 << 32 || ds->first_index + B > (int64_t)1 << 32)
+            return fail(h, ALIPMPC_EINVAL, "closed loop dataset: first_index < 0 or first_index + B > 2^32");
+        if (!(ds->safe_dis >= 0) || !std::isfinite(ds->safe_dis))
+            return fail(h, ALIPMPC_EINVAL, "closed loop dataset: safe_dis negative or not finite");
+        if (ds->max_rows < 0) return fail(h, ALIPMPC_EINVAL, "closed loop dataset: max_rows < 0");
+        if ((long long)S * f_cyc * ncx > 0x7fffffffLL)
+            return fail(h, ALIPMPC_EINVAL, "closed loop dataset: S * f_cyc * columns of X > 2^31 - 1");
+        if (B == 0 || S == 0) {   // no rows: row_start is all zero
+            if (ds->row_start) {
+                if (hip_stream == nullptr) {
+                    std::memset(ds->row_start, 0, ((size_t)B + 1) * 8);
+                } else {
+                    HIPCHK(h, hipSetDevice(h->device));
+                    HIPCHK(h, hipMemsetAsync(ds->row_start, 0, ((size_t)B + 1) * 8, stream_of(h, hip_stream)));
+                }
+            }
+            return ALIPMPC_OK;
+        }
+    }
     if (B == 0 || S == 0) return ALIPMPC_OK;
     if (!x0 || !foot0 || !goal || !leg || !nc || (cf.nc_max > 0 && !cir) || (cf.ne_max > 0 && (!elp || !ne)))
         return fail(h, ALIPMPC_EINVAL, "missing input pointer");
@@ -6273,6 +6336,9 @@ int alipmpc_closed_loop_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc,
     const size_t Bz = (size_t)B, Sz = (size_t)S, Fz = (size_t)f_cyc;
     hipStream_t st = stream_of(h, hip_stream);
     const bool host = hip_stream == nullptr;
+    // dataset: are rows wanted (or row_start alone), and the rows the host-mode copies of the row arrays hold
+    const bool ds_rows = ds && (ds->X || ds->y_mpc || ds->y_act || ds->row_status);
+    const size_t ds_cap = ds ? std::min<size_t>((size_t)ds->max_rows, Bz * Sz * Fz) : 0;
     auto layout = [&](Carver& cv, bool take_io) {
         struct L {
             double *x, *pst, *hdv, *mhd, *plan, *xs, *u0, *u, *foot, *xp;
@@ -6282,6 +6348,9 @@ int alipmpc_closed_loop_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc,
             double *goal, *cir, *elp, *ft, *xt, *hd, *actd;
             int32_t *nc, *ne, *stt, *itt, *sg;
             double *vdes, *pose0;
+            double *ds_tick, *ds_step, *dX, *dym, *dya;
+            int32_t *ds_nst, *drs;
+            long long* ds_rs;
         } l{};
         l.vdes = cv.take<double>(Bz * 2); l.pose0 = cv.take<double>(Bz * 3);
         l.x = cv.take<double>(Bz * 5); l.pst = cv.take<double>(Bz * 2); l.hdv = cv.take<double>(Bz * 4);
@@ -6298,6 +6367,21 @@ int alipmpc_closed_loop_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc,
             l.itt = cv.take<int32_t>(Bz * Sz * Fz); l.sg = cv.take<int32_t>(Bz);
             if (action_traj) l.actd = cv.take<double>(Bz * Sz * Fz * 8);
         }
+        if (ds) {   // after everything the existing call carves
+            l.ds_rs = cv.take<long long>(Bz + 1);
+            l.ds_nst = cv.take<int32_t>(Bz);
+            if (ds_rows) {
+                l.ds_step = cv.take<double>(Bz * Sz * DS_STEP);
+                l.ds_tick = cv.take<double>(Bz * Sz * Fz * DS_TICK);
+                if (!take_io && ds->row_status && !status_traj) l.stt = cv.take<int32_t>(Bz * Sz * Fz);
+                if (take_io) {
+                    if (ds->X) l.dX = cv.take<double>(ds_cap * (size_t)ncx);
+                    if (ds->y_mpc) l.dym = cv.take<double>(ds_cap * 8);
+                    if (ds->y_act) l.dya = cv.take<double>(ds_cap * 8);
+                    if (ds->row_status) l.drs = cv.take<int32_t>(ds_cap);
+                }
+            }
+        }
         return l;
     };
     size_t need;
@@ -6310,7 +6394,12 @@ int alipmpc_closed_loop_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc,
         if (h->rstage) hipFree(h->rstage);
         h->rstage = nullptr;
         h->rstage_bytes = 0;
-        HIPCHK(h, hipMalloc(&h->rstage, need));
+        if (hipError_t e = hipMalloc(&h->rstage, need); e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, ALIPMPC_EHIP, "closed loop: workspace of " + std::to_string(need) + " bytes" +
+                        (ds_rows ? " (row staging " + std::to_string(Bz * Sz * Fz * DS_TICK * 8) + " bytes)" : "") +
+                        ": " + hipGetErrorString(e));
+        }
         h->rstage_bytes = need;
     }
     Carver cv{(char*)h->rstage};
@@ -6340,6 +6429,7 @@ int alipmpc_closed_loop_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc,
         d_sg = steps_to_goal ? l.sg : nullptr;
         d_act = action_traj ? l.actd : nullptr;
     }
+    if (ds_rows && ds->row_status && !d_stt) d_stt = l.stt;   // row_status is compacted from the ticks' statuses
     CLP C;
     std::memset(&C, 0, sizeof(C));
     C.B = B; C.S = S; C.f = f_cyc; C.variant = cf.variant; C.N = N; C.kick = kick; C.seed = (unsigned long long)seed;
@@ -6349,6 +6439,7 @@ int alipmpc_closed_loop_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc,
     C.foot_traj = d_ft; C.x_traj = d_xt; C.hd_traj = d_hd; C.status_traj = d_stt; C.iters_traj = d_itt;
     C.steps_to_goal = d_sg;
     C.action_traj = d_act; C.vdes = l.vdes; C.pose0 = l.pose0;
+    C.ds_tick = l.ds_tick; C.ds_step = l.ds_step; C.ds_nst = l.ds_nst;
     const double beta = std::sqrt(cf.g / cf.H), T = cf.dt, dt = T / f_cyc;
     {   // alip_des_vel(0.6, leg_ind) (MPC_LIP_modi.py:181-186)
         const double sh = std::sinh(beta * T), ch = std::cosh(beta * T);
@@ -6393,12 +6484,13 @@ int alipmpc_closed_loop_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc,
         };
         CLP c = C;
         c.B = Bg;
-        c.b0 = b0;
+        c.b0 = (ds ? (long long)ds->first_index : 0) + b0;
         o(c.goal, 2); o(c.x, 5); o(c.pst, 2); o(c.hdv, 4); o(c.mhd, 3); o(c.plan, nn); o(c.leg, 1); o(c.flags, 1);
         o(c.xs, 5); o(c.u0, nn); o(c.sleg, 1); o(c.u, nn); o(c.foot, 3); o(c.x_pred, nn); o(c.status, 1);
         o(c.iters, 1); o(c.active, 1); o(c.foot_traj, 3LL * S); o(c.x_traj, 5LL * (S + 1)); o(c.hd_traj, 2LL * S);
         o(c.status_traj, SF); o(c.iters_traj, SF); o(c.steps_to_goal, 1); o(c.action_traj, 8 * SF); o(c.vdes, 2);
         o(c.pose0, 3);
+        o(c.ds_tick, DS_TICK * SF); o(c.ds_step, (long long)DS_STEP * S); o(c.ds_nst, 1);
         KP q = P;
         q.B = Bg;
         o(q.goal, 2); o(q.cir, 3LL * cf.nc_max); o(q.nc, 1); o(q.elp, 5LL * cf.ne_max); o(q.ne, 1); o(q.x0, 5);
@@ -6468,9 +6560,40 @@ int alipmpc_closed_loop_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc,
             HIPCHK(h, hipStreamWaitEvent(st, h->gev[g], 0));
         }
     }
+    long long* d_rs = nullptr;
+    if (ds) {   // rows: scan the steps entered into row_start, then one wavefront per episode compacts its rows
+        d_rs = host || !ds->row_start ? l.ds_rs : (long long*)ds->row_start;
+        hipLaunchKernelGGL(ds_scan_kernel, dim3(1), dim3(DS_SCAN_THREADS), 0, st, (const int32_t*)l.ds_nst,
+                           (long long)B, (int)f_cyc, d_rs);
+        HIPCHK(h, hipGetLastError());
+        if (ds_rows && ds->max_rows > 0) {
+            DsP D;
+            std::memset(&D, 0, sizeof(D));
+            D.B = B; D.max_rows = ds->max_rows; D.S = S; D.f = f_cyc; D.nc_max = cf.nc_max; D.ne_max = cf.ne_max;
+            D.safe = ds->safe_dis; D.T = T; D.Td = T / f_cyc;
+            D.tick = l.ds_tick; D.step = l.ds_step; D.stt = d_stt;
+            D.cir = d_cir; D.nc = d_nc; D.elp = d_elp; D.ne = d_ne; D.goal = d_goal; D.row_start = d_rs;
+            D.X = host ? l.dX : ds->X; D.y_mpc = host ? l.dym : ds->y_mpc; D.y_act = host ? l.dya : ds->y_act;
+            D.row_status = host ? l.drs : ds->row_status;
+            constexpr int WPB = 256 / WAVE;
+            hipLaunchKernelGGL(ds_compact_kernel, dim3((unsigned)((B + WPB - 1) / WPB)), dim3(256), 0, st, D);
+            HIPCHK(h, hipGetLastError());
+        }
+    }
     HIPCHK(h, hipEventRecord(h->ev[ei][1], st));
     h->evlast = ei;
     h->timed = true;
+    if (host && ds) {   // the total first: only the rows that exist (and fit) are copied back
+        std::vector<long long> rs(Bz + 1);
+        HIPCHK(h, hipMemcpyAsync(rs.data(), d_rs, (Bz + 1) * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipStreamSynchronize(st));
+        if (ds->row_start) std::memcpy(ds->row_start, rs.data(), (Bz + 1) * 8);
+        const size_t nr = std::min<size_t>((size_t)rs[Bz], ds_cap);
+        if (nr && ds->X) HIPCHK(h, hipMemcpyAsync(ds->X, l.dX, nr * ncx * 8, hipMemcpyDeviceToHost, st));
+        if (nr && ds->y_mpc) HIPCHK(h, hipMemcpyAsync(ds->y_mpc, l.dym, nr * 8 * 8, hipMemcpyDeviceToHost, st));
+        if (nr && ds->y_act) HIPCHK(h, hipMemcpyAsync(ds->y_act, l.dya, nr * 8 * 8, hipMemcpyDeviceToHost, st));
+        if (nr && ds->row_status) HIPCHK(h, hipMemcpyAsync(ds->row_status, l.drs, nr * 4, hipMemcpyDeviceToHost, st));
+    }
     if (host) {
         if (foot_traj) HIPCHK(h, hipMemcpyAsync(foot_traj, l.ft, Bz * Sz * 3 * 8, hipMemcpyDeviceToHost, st));
         if (x_traj) HIPCHK(h, hipMemcpyAsync(x_traj, l.xt, Bz * (Sz + 1) * 5 * 8, hipMemcpyDeviceToHost, st));
@@ -6482,6 +6605,29 @@ int alipmpc_closed_loop_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc,
         HIPCHK(h, hipStreamSynchronize(st));
     }
     return ALIPMPC_OK;
+}
+
+int alipmpc_closed_loop_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc, double kick, uint64_t seed,
+                              const double* x0, const double* foot0, const double* goal, const int8_t* leg,
+                              const double* cir, const int32_t* nc, const double* elp, const int32_t* ne,
+                              double* foot_traj, double* x_traj, double* hd_traj, int32_t* status_traj,
+                              int32_t* iters_traj, int32_t* steps_to_goal, double* action_traj, void* hip_stream)
+{
+    return closed_loop_impl((Handle*)handle, B, S, f_cyc, kick, seed, x0, foot0, goal, leg, cir, nc, elp, ne, foot_traj,
+                            x_traj, hd_traj, status_traj, iters_traj, steps_to_goal, action_traj, hip_stream, nullptr);
+}
+
+int alipmpc_closed_loop_dataset_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc, double kick, uint64_t seed,
+                                      const double* x0, const double* foot0, const double* goal, const int8_t* leg,
+                                      const double* cir, const int32_t* nc, const double* elp, const int32_t* ne,
+                                      double* foot_traj, double* x_traj, double* hd_traj, int32_t* status_traj,
+                                      int32_t* iters_traj, int32_t* steps_to_goal, double* action_traj,
+                                      int64_t first_index, double safe_dis, int64_t max_rows, double* X, double* y_mpc,
+                                      double* y_act, int32_t* row_status, int64_t* row_start, void* hip_stream)
+{
+    const DsArgs ds{first_index, safe_dis, max_rows, X, y_mpc, y_act, row_status, row_start};
+    return closed_loop_impl((Handle*)handle, B, S, f_cyc, kick, seed, x0, foot0, goal, leg, cir, nc, elp, ne, foot_traj,
+                            x_traj, hd_traj, status_traj, iters_traj, steps_to_goal, action_traj, hip_stream, &ds);
 }
 
 int32_t alipmpc_trace_len(const alipmpc_cfg* cfg)

@@ -19,6 +19,10 @@ Fixtures written
                                        the reference NLP reproduces (<1e-6)
   g3_synthetic_{modi,sig_step,dd}.npz  random 5-obstacle scenes solved to a tight KKT point by two scipy
                                        methods on the reference callbacks; kept where both agree
+  g6_sup_learn_rows.npz                the first 160 recorded rows (20 walking steps of f_cyc = 8 MPC calls) of
+                                       sup_learn/X_data.csv, y_mpc_data.csv and y_act_data.csv as recorded
+                                       (data_procs/logger_iml.py:377-401, 416-428): the rows alipmpc.dataset.check_rows
+                                       is validated on
   g4_aux.npz                           get_next_states, xk_track_det, alip_des_vel, cal_foot_with_veldes,
                                        constant matrices A, B, W, M_A, M_B, dx_du, dP_du
 
@@ -734,6 +738,16 @@ def gen_g5_logger():
     print("g5 logger written")
 
 
+def gen_g6_sup_learn_rows(rows=160, f_cyc=8):
+    """The first `rows` recorded rows of the reference's three dataset files, unchanged (recorded data only)."""
+    names = dict(X="X_data.csv", y_mpc="y_mpc_data.csv", y_act="y_act_data.csv")
+    R = {k: np.loadtxt(os.path.join(REF, "sup_learn", v), delimiter=",")[:rows] for k, v in names.items()}
+    assert all(len(v) == rows for v in R.values()) and rows % f_cyc == 0
+    R["f_cyc"] = np.int32(f_cyc)
+    np.savez_compressed(os.path.join(OUT, "g6_sup_learn_rows.npz"), **R)
+    print(f"g6 sup_learn rows: {rows} rows, X {R['X'].shape}, y_mpc {R['y_mpc'].shape}, y_act {R['y_act'].shape}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
@@ -743,8 +757,12 @@ def main():
         print("reference not present; nothing to do")
         return 0
     os.makedirs(OUT, exist_ok=True)
-    modi, sig, dd, rand_obs = import_reference()
     only = set(a.only.split(",")) if a.only else None
+    if not only or "g6" in only:
+        gen_g6_sup_learn_rows()
+    if only == {"g6"}:   # (recorded data only: the reference's modules are not needed)
+        return 0
+    modi, sig, dd, rand_obs = import_reference()
     if not only or "g1" in only:
         gen_g1(modi, sig, dd, rand_obs, 24 if a.quick else 64)
     if not only or "g2" in only:
