@@ -330,12 +330,53 @@ __device__ __forceinline__ double bcast(double v, int src)
     return __hiloint2double(hi, lo);
 }
 
+// dev A/B switches (r8): each restores the earlier form of one change, with the same bits
+#ifdef ALIP_NO_RBCAST
+#define ALIP_RBCAST 0   // broadcasts of the Gauss-Jordan rows / dp through readlane instead of row_newbcast
+#else
+#define ALIP_RBCAST 1
+#endif
+#ifdef ALIP_NO_WRED2
+#define ALIP_WRED2 0    // one butterfly per reduced value instead of two values per butterfly
+#else
+#define ALIP_WRED2 1
+#endif
+#ifdef ALIP_NO_DPP_BC
+constexpr bool DPP_BC = false;   // DPP moves with an explicit zero "old" value (two v_mov per 64-bit move)
+#else
+// bound_ctrl on every DPP move: lanes without a valid source read 0, which is what the old value 0 gave them, and
+// with the full row / bank masks the compiler then needs no old value at all — no v_mov 0 pair (and no wait state
+// behind it) in front of each move.  The same values in every lane.
+constexpr bool DPP_BC = true;
+#endif
+#ifdef ALIP_NO_PACKF
+#define ALIP_PACKF 0    // wave-uniform scalar functions once per argument instead of once for all
+#else
+#define ALIP_PACKF 1
+#endif
+
+// row broadcast: every lane receives v of lane P of its own 16-lane row (one DPP move, 64-bit for a double; the
+// consumer reads the VGPRs directly, no SGPR round trip).  Equals bcast(v, P) in row 0 only: for values whose source
+// and consumers all sit in lanes 0..15 (the Gauss-Jordan rows), or after the value was replicated into the other rows.
+template <int P>
+__device__ __forceinline__ double rbcast(double v)
+{
+    static_assert(P >= 0 && P < 16, "row_newbcast selects a lane of the row");
+    return __builtin_amdgcn_update_dpp(0.0, v, 0x150 + P, 0xF, 0xF, true);
+}
+template <int P>
+__device__ __forceinline__ float rbcast(float v)
+{
+    static_assert(P >= 0 && P < 16, "row_newbcast selects a lane of the row");
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x150 + P, 0xF, 0xF, true));
+}
+
 // ---- cross-lane exchange without LDS: DPP within 16-lane rows, permlane swaps across rows
 template <int CTRL>
 __device__ __forceinline__ double dpp(double v)
 {
-    int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
-    int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
+    int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, DPP_BC);
+    int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, DPP_BC);
     return __hiloint2double(hi, lo);
 }
 // returns (v[l], v[l ^ 16]) / (v[l], v[l ^ 32]) as the symmetric pair (a, b)
@@ -366,7 +407,7 @@ __device__ __forceinline__ float bcast(float v, int src)
 template <int CTRL>
 __device__ __forceinline__ float dpp(float v)
 {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, DPP_BC));
 }
 __device__ __forceinline__ void swap16(float v, float& a, float& b)
 {
@@ -409,6 +450,54 @@ __device__ __forceinline__ T wreduce(T v, Op op)
     v = op(a, b);
     swap32(v, a, b);
     return uni(op(a, b));
+}
+// two values, one operator, one butterfly: a <- wreduce(a), b <- wreduce(b).  At the first step (l ^ 1) even lanes keep
+// a and odd lanes keep b, each taking the partner's copy of the value it keeps; from there the lanes of one parity
+// carry one reduction.  The steps inside a row keep the parity with rotations by 4 and by 8 (the mirrors of wreduce
+// would cross it): quad 0 combines with quad 1, quad 2 with quad 3, then the half-rows, then the rows as in wreduce —
+// every partial is op(own, partner) over wreduce's pairing tree, and op is commutative (IEEE add / max / min), so
+// lanes 0 and 1 end with the bits wreduce gives (NaN payloads aside).
+template <class T, class Op>
+__device__ __forceinline__ void wreduce2(T& a, T& b, Op op)
+{
+#if ALIP_WRED2
+    const bool odd = (lane_id() & 1) != 0;
+    const T keep = odd ? b : a, give = odd ? a : b;
+    T v = op(keep, dpp<0xB1>(give));
+    v = op(v, dpp<0x4E>(v));
+    v = op(v, dpp<0x12C>(v));   // row_ror:12: lane l reads lane (l + 4) & 15
+    v = op(v, dpp<0x128>(v));   // row_ror:8:  lane l reads lane l ^ 8
+    T x, y;
+    swap16(v, x, y);
+    v = op(x, y);
+    swap32(v, x, y);
+    v = op(x, y);
+    a = bcast(v, 0);
+    b = bcast(v, 1);
+#else
+    a = wreduce(a, op);
+    b = wreduce(b, op);
+#endif
+}
+template <class T>
+__device__ __forceinline__ void wsum_pair(T& a, T& b) { wreduce2(a, b, OpAdd()); }
+template <class T>
+__device__ __forceinline__ void wmax_pair(T& a, T& b) { wreduce2(a, b, OpMax()); }
+template <class T>
+__device__ __forceinline__ void wmin_pair(T& a, T& b) { wreduce2(a, b, OpMin()); }
+// hi <- wmax(hi), lo <- wmin(lo) in one butterfly: wmin(x) = -wmax(-x) exactly (negation is exact and
+// max(-x, -y) = -min(x, y) for every pair, infinities and signed zeros included)
+template <class T>
+__device__ __forceinline__ void wmaxmin_pair(T& hi, T& lo)
+{
+#if ALIP_WRED2
+    T nlo = -lo;
+    wreduce2(hi, nlo, OpMax());
+    lo = -nlo;
+#else
+    hi = wreduce(hi, OpMax());
+    lo = wreduce(lo, OpMin());
+#endif
 }
 template <class T>
 __device__ __forceinline__ T wsum(T v) { return wreduce(v, OpAdd()); }
@@ -708,6 +797,38 @@ __device__ __forceinline__ float rcp_nr(float x)
 
 #include "fastmath.inc"
 
+// ---- wave-uniform scalar functions, once for several arguments (r8): lane i evaluates argument i and the results
+// are read back from lanes 0, 1, 2 — the same function on the same argument, so the bits of separate calls, for
+// one copy of the instruction sequence and one dependent chain instead of one per argument
+template <class T>
+__device__ __forceinline__ void llog3(T x0, T x1, T x2, T& l0, T& l1, T& l2)
+{
+#if ALIP_PACKF
+    const int l = lane_id();
+    const T r = llog(l == 0 ? x0 : (l == 1 ? x1 : x2));
+    l0 = bcast(r, 0);
+    l1 = bcast(r, 1);
+    l2 = bcast(r, 2);
+#else
+    l0 = uni(llog(x0));
+    l1 = uni(llog(x1));
+    l2 = uni(llog(x2));
+#endif
+}
+// the convergence test's scalings max(100, nz / den) / 100 for two denominators (IPOPT's s_d and s_c)
+template <class T>
+__device__ __forceinline__ void err_scales(T nz, T den0, T den1, T& sd, T& sc)
+{
+#if ALIP_PACKF
+    const T r = div100(fmax(T(100.0), rcp_div(nz, lane_id() == 1 ? den1 : den0)));
+    sd = bcast(r, 0);
+    sc = bcast(r, 1);
+#else
+    sd = uni(div100(fmax(T(100.0), rcp_div(nz, den0))));
+    sc = uni(div100(fmax(T(100.0), rcp_div(nz, den1))));
+#endif
+}
+
 template <int N, class WT>
 __device__ void prologue(const KP& P, const WT& w, const typename WT::real* G, const double* E,
                          long long b, double& gxg, double& gyg, int& legv, double& uj)
@@ -912,26 +1033,72 @@ __device__ __forceinline__ bool gj_lds(R* M, int lane)
 // a[0..n]; step p reads the pivot row's entries j > p by readlane (uniform), scales them by 1 / pivot and updates
 // every other row — gj_lds's arithmetic element for element, without an LDS round trip per step (the steps are a
 // readlane -> rcp -> fma chain).  On success lane i holds x_i in a[n].
-template <int n, class R>
-__device__ __forceinline__ bool gj_regs(R (&a)[n + 1], int lane)
+//
+// r8 (RB): the pivot row's entries reach the other rows by a row broadcast (rbcast: one 64-bit DPP move that the fma
+// reads directly) instead of a readlane pair through SGPRs.  Rows live in lanes 0..n-1 of row 0 (n <= 16), so lanes
+// 0..15 see exactly what readlane gave them; lanes 16..63 hold no row (their a[] is never read afterwards).  The
+// pivot itself stays a readlane: its test is a wave-uniform branch.  fp32 keeps readlane (one instruction already).
+// Only the shapes with one row group per lane take it (gj_rb): a row broadcast needs a VGPR pair where readlane used
+// SGPRs, and with two row groups (N = 5, n = 15, already at 256 VGPRs) that pair cost 144 B/lane of new spills and
+// 9 % of cfg3 (15.25 -> 16.69 ms per step, profiles/r8/ab_cfg3.log).
+template <int RPL>
+constexpr bool gj_rb = ALIP_RBCAST != 0 && RPL == 1;
+template <int p, int n, bool RB, class R>
+__device__ __forceinline__ bool gj_steps(R (&a)[n + 1], int lane)
 {
-    // r4: the pivot row is not normalised during the elimination (row i -= (a_ip / a_pp) row p for i != p; row p
-    // stays), so no per-entry select between the pivot row and the others; the diagonal left at the end divides the
-    // right-hand side once per lane.  The pivots a_pp are the same D of K = L D L^T (the positive-definiteness test).
-#pragma unroll
-    for (int p = 0; p < n; ++p) {
+    if constexpr (p < n) {
         const R d = bcast(a[p], p);
         if (!(d > R(0))) return false;   // wave-uniform
         const R m = lane == p ? R(0) : a[p] * rcp_nr(d);
 #pragma unroll
-        for (int j = p + 1; j <= n; ++j) a[j] = fma(-m, bcast(a[j], p), a[j]);
+        for (int j = p + 1; j <= n; ++j) {
+            if constexpr (RB && sizeof(R) == 8)
+                a[j] = fma(-m, rbcast<p>(a[j]), a[j]);
+            else
+                a[j] = fma(-m, bcast(a[j], p), a[j]);
+        }
+        return gj_steps<p + 1, n, RB>(a, lane);
+    } else {
+        return true;
     }
+}
+template <int n, class R, bool RB>
+__device__ __forceinline__ bool gj_regs(R (&a)[n + 1], int lane)
+{
+    static_assert(n <= 16, "the rows sit in one 16-lane row");
+    // r4: the pivot row is not normalised during the elimination (row i -= (a_ip / a_pp) row p for i != p; row p
+    // stays), so no per-entry select between the pivot row and the others; the diagonal left at the end divides the
+    // right-hand side once per lane.  The pivots a_pp are the same D of K = L D L^T (the positive-definiteness test).
+    if (!gj_steps<0, n, RB>(a, lane)) return false;
     // lane i: x_i = a_i[n] / a_i[i]
     R dg = a[0];
 #pragma unroll
     for (int i = 1; i < n; ++i) dg = lane == i ? a[i] : dg;
     a[n] = a[n] * rcp_nr(dg);
     return true;
+}
+
+// dV = G dp with dp from gj_regs (lane j < n holds dp_j, the other lanes 0): generator rows sit in lanes 0..NG-1.
+// With NG <= 32 one permlane16 swap copies dp into row 1 and every dp_j is a row broadcast; the sum runs over j in
+// the same order with the same fma as the readlane form.
+template <int n, int NG, class R>
+constexpr bool dp_rows = ALIP_RBCAST != 0 && sizeof(R) == 8 && n <= 16 && NG <= 32;
+template <int j, int n, class R>
+__device__ __forceinline__ R gdp_acc(const R* Grow, R x, R v)
+{
+    if constexpr (j < n) {
+        v += Grow[j] * rbcast<j>(x);
+        return gdp_acc<j + 1, n>(Grow, x, v);
+    } else {
+        return v;
+    }
+}
+template <int n, int NCP, class R>
+__device__ __forceinline__ R gdp_rows(const R* G, R xv, int t)
+{
+    R x0, x1;
+    swap16(xv, x0, x1);   // x0: rows 0 and 1 both hold row 0's xv (the swap's first result is [r0, r0, r2, r2])
+    return gdp_acc<0, n>(G + t * NCP, x0, R(0.0));
 }
 
 // working copy for gj_lds: M[i][j] = K[i][j] + dw [i == j] (j <= n; column n = rhs), same element
@@ -1869,11 +2036,10 @@ __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, lo
             nz = wsum(nz);
             // (r4: divisions as rcp_div / div100 — a reciprocal and its residual correction instead of the IEEE
             // division sequence)
-            const R sd = uni(div100(fmax(R(100.0), rcp_div(nz, w.cst[K_MACT] + n))));
-            const R sc = uni(div100(fmax(R(100.0), rcp_div(nz, fmax(R(1.0), w.cst[K_NBL])))));
+            R sd, sc;
+            err_scales(nz, w.cst[K_MACT] + n, fmax(R(1.0), w.cst[K_NBL]), sd, sc);
             const R base_err = wmax(fmax(rcp_div(ru, sd), rcm));
-            whi = wmax(whi);
-            wlo = wmin(wlo);
+            wmaxmin_pair(whi, wlo);
             const bool anyw = whi >= wlo;
             const R comp0 = anyw ? fmax(fabs(whi), fabs(wlo)) : R(0.0);
             e0 = uni(fmax(base_err, rcp_div(comp0, sc)));
@@ -2047,11 +2213,11 @@ __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, lo
                     a[n] = rhs_l + R(0.0);
                 };
                 fill(R(0));
-                if (!gj_regs<n>(a, lane)) {
+                if (!gj_regs<n, R, gj_rb<RPL>>(a, lane)) {
                     R dw = dw_last == R(0.0) ? R(1e-4) : fmax(R(1e-20), dw_last / R(3.0));
                     for (;;) {
                         fill(dw);
-                        if (gj_regs<n>(a, lane)) break;
+                        if (gj_regs<n, R, gj_rb<RPL>>(a, lane)) break;
                         dw *= dw_last == R(0.0) ? R(100.0) : R(8.0);
                         if (dw > R(sizeof(R) == 8 ? 1e40 : 1e30)) {   // (not IPOPT's 1e20)
                             fact_ok = false;
@@ -2135,9 +2301,13 @@ __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, lo
         RELANE();
         {
             R v = R(0.0);
+            if constexpr (GJ && GJ_REGS && dp_rows<n, NG, R>) {
+                v = gdp_rows<n, NCP>(G, xv, lane < NG ? lane : 0);
+            } else {
 #pragma unroll
-            for (int j = 0; j < n; ++j)
-                v += G[(lane < NG ? lane : 0) * NCP + j] * (GJ && !GJ_REGS ? w.S[j * GJLD + n] : bcast(xv, j));
+                for (int j = 0; j < n; ++j)
+                    v += G[(lane < NG ? lane : 0) * NCP + j] * (GJ && !GJ_REGS ? w.S[j * GJLD + n] : bcast(xv, j));
+            }
             // a factorisation the regularisation could not rescue: zero step (the iterate stays), and the
             // solve ends at the next iteration's test with status -3 (no extra loop exit here: an exit
             // edge in mid-iteration lengthens live ranges and costs spills)
@@ -2178,8 +2348,7 @@ __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, lo
             theta += fabs(rcv[q]);
             sl += (HL(q) ? dS[q] * idl[q] : R(0.0)) - (HU(q) ? dS[q] * idu[q] : R(0.0));
         }
-        ap = wmin(ap);
-        az = wmin(az);
+        wmin_pair(ap, az);
         // theta = sum |c - s| at the current point: the accepted trial's value (same operations, same order)
         // unless the point came from the initial set-up or a restoration reset
         theta = theta_ok ? theta_c : wsum(theta);
@@ -2188,8 +2357,10 @@ __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, lo
         const R phi = uni(f_cur - mu * lsum_cur);
         const R gphi = uni(gdv - mu * sl);
         // switching condition a (-gphi)^s_phi > theta^s_theta in log space: log a + s_phi llog(-gphi) >
-        // s_theta log theta (two logs per iteration instead of two pow per trial)
-        const R lsw = uni(gphi < 0 ? sth * llog(theta) - sph * llog(-gphi) : R(0.0));
+        // s_theta log theta (two logs per iteration instead of two pow per trial); the search's log a with them
+        R lth, lgp, lap;
+        llog3(theta, -gphi, ap, lth, lgp, lap);
+        const R lsw = uni(gphi < 0 ? sth * lth - sph * lgp : R(0.0));
         R amin;
         if (gphi < 0) {
             amin = fmin(gth, gph * theta / -gphi);
@@ -2209,7 +2380,7 @@ __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, lo
         // the first accepting one re-evaluates that trial: the same trials, the same arithmetic, the same choice as one
         // wave.
         R a = ap;
-        R la = uni(llog(ap));   // log a, tracked exactly through the halvings
+        R la = lap;   // log a, tracked exactly through the halvings
         bool accepted = false, ftype = false;
         R ctr[RPL], ta0[RPL], ta1[RPL];
         R ft = R(0.0), lgt = R(0.0), tht_acc = R(0.0);
@@ -2251,9 +2422,8 @@ __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, lo
                     // logs had compiled to three log evaluations per trial
                     lgt += llog(HL(q) ? (HU(q) ? d1 * d2 : d1) : (HU(q) ? d2 : R(1.0)));
                 }
-                tht = wsum(tht);
+                wsum_pair(tht, lgt);
                 ft = obj_sum<N, RPL>(ctr, mr4);
-                lgt = wsum(lgt);
                 const bool anybad = __ballot(bad) != 0ull;
                 const R pht = anybad ? INFINITY : ft - mu * lgt;
                 bool ok = isfinite(pht) && tht < w.cst[K_THMAX];
@@ -5205,6 +5375,83 @@ hipError_t launch_sweep(int nc, bool fen, const KP& P, hipStream_t st)
 }
 #endif
 
+#if ALIP_PART_HOST
+// ------------------------------------------------------------------------------------------------
+// test hook (alipmpc_dbg_wave_helpers, tests/test_wave_helpers_gpu.py): the r8 wave helpers next to the forms they
+// replaced, one wave.  Set s reads a = in[128 s + lane], b = in[128 s + 64 + lane] and writes WH_SET doubles:
+//    0.. 5  wreduce: sum a, sum b, max a, max b, min a, min b        6..11  the same through wreduce2
+//   12, 13  wmax(a), wmin(b)                                        14, 15  wmaxmin_pair(a, b)
+//   16..18  llog of a[0..2], one call each                          19..21  llog3
+//   22, 23  the error scalings of nz = b[0] over b[1], b[2]         24, 25  err_scales
+//   32 + 64 P + lane            a of lane P of the lane's row by readlane (P = 0..15)
+//   32 + 1024 + 64 P + lane     rbcast<P>(a)
+// System m reads the 9 x 10 rows [K | rhs] at sys[90 m] and writes 20 doubles: x[0..8] and the pivot verdict of
+// gj_regs with readlane broadcasts, then with row broadcasts.
+// ------------------------------------------------------------------------------------------------
+constexpr int WH_SET = 32 + 2 * 16 * WAVE;
+template <int P>
+__device__ __forceinline__ void wh_bcasts(double a, double* o, int lane)
+{
+    if constexpr (P < 16) {
+        const double r0 = bcast(a, P), r1 = bcast(a, 16 + P), r2 = bcast(a, 32 + P), r3 = bcast(a, 48 + P);
+        o[WAVE * P + lane] = lane < 16 ? r0 : (lane < 32 ? r1 : (lane < 48 ? r2 : r3));
+        o[16 * WAVE + WAVE * P + lane] = rbcast<P>(a);
+        wh_bcasts<P + 1>(a, o, lane);
+    }
+}
+__global__ __launch_bounds__(WAVE) void wave_helpers_kernel(const double* in, int nsets, const double* sys, int nsys,
+                                                            double* out, double* gj_out)
+{
+    const int lane = lane_id();
+    for (int s = 0; s < nsets; ++s) {
+        const double a = in[2 * WAVE * s + lane], b = in[2 * WAVE * s + WAVE + lane];
+        double* o = out + (size_t)WH_SET * s;
+        double r[26];
+        r[0] = wreduce(a, OpAdd()); r[1] = wreduce(b, OpAdd());
+        r[2] = wreduce(a, OpMax()); r[3] = wreduce(b, OpMax());
+        r[4] = wreduce(a, OpMin()); r[5] = wreduce(b, OpMin());
+        r[6] = a; r[7] = b;
+        wsum_pair(r[6], r[7]);
+        r[8] = a; r[9] = b;
+        wmax_pair(r[8], r[9]);
+        r[10] = a; r[11] = b;
+        wmin_pair(r[10], r[11]);
+        r[12] = wreduce(a, OpMax()); r[13] = wreduce(b, OpMin());
+        r[14] = a; r[15] = b;
+        wmaxmin_pair(r[14], r[15]);
+        const double a0 = bcast(a, 0), a1 = bcast(a, 1), a2 = bcast(a, 2);
+        r[16] = uni(llog(a0)); r[17] = uni(llog(a1)); r[18] = uni(llog(a2));
+        llog3(a0, a1, a2, r[19], r[20], r[21]);
+        const double nz = bcast(b, 0), d0 = bcast(b, 1), d1 = bcast(b, 2);
+        r[22] = uni(div100(fmax(100.0, rcp_div(nz, d0))));
+        r[23] = uni(div100(fmax(100.0, rcp_div(nz, d1))));
+        err_scales(nz, d0, d1, r[24], r[25]);
+        double mine = 0.0;
+#pragma unroll
+        for (int i = 0; i < 26; ++i) mine = lane == i ? r[i] : mine;
+        if (lane < 26) o[lane] = mine;
+        wh_bcasts<0>(a, o + 32, lane);
+    }
+    for (int m = 0; m < nsys; ++m) {
+        constexpr int n = 9;
+        double a[n + 1], c[n + 1];
+#pragma unroll
+        for (int j = 0; j <= n; ++j) a[j] = c[j] = lane < n ? sys[(n + 1) * (n * m + lane) + j] : 0.0;
+        const bool ok_a = gj_regs<n, double, false>(a, lane);
+        const bool ok_c = gj_regs<n, double, true>(c, lane);
+        double* o = gj_out + 2 * (n + 1) * m;
+        if (lane < n) {
+            o[lane] = a[n];
+            o[n + 1 + lane] = c[n];
+        }
+        if (lane == n) {
+            o[n] = ok_a ? 1.0 : 0.0;
+            o[2 * n + 1] = ok_c ? 1.0 : 0.0;
+        }
+    }
+}
+#endif
+
 }  // namespace alip
 
 #if ALIP_PART_HOST
@@ -6838,6 +7085,29 @@ int alipmpc_dbg_wstamps(unsigned long long* out, long long slots)
     return (int)slots;
 }
 #endif
+
+// test hook (not part of the ABI): wave_helpers_kernel on host arrays — in (nsets x 128), sys (nsys x 90),
+// out (nsets x alip::WH_SET), gj_out (nsys x 20); returns alip::WH_SET, or -1 on a HIP error
+int alipmpc_dbg_wave_helpers(const double* in, int nsets, const double* sys, int nsys, double* out, double* gj_out)
+{
+    if (nsets < 0 || nsys < 0 || nsets > 4096 || nsys > 4096) return -1;
+    const size_t zi = sizeof(double) * 2 * alip::WAVE * (size_t)nsets, zs = sizeof(double) * 90 * (size_t)nsys;
+    const size_t zo = sizeof(double) * alip::WH_SET * (size_t)nsets, zg = sizeof(double) * 20 * (size_t)nsys;
+    double* d = nullptr;
+    if (hipMalloc((void**)&d, zi + zs + zo + zg + 8) != hipSuccess) return -1;
+    double *di = d, *ds = di + 2 * alip::WAVE * (size_t)nsets, *dout = ds + 90 * (size_t)nsys,
+           *dg = dout + alip::WH_SET * (size_t)nsets;
+    bool ok = (zi == 0 || hipMemcpy(di, in, zi, hipMemcpyHostToDevice) == hipSuccess) &&
+              (zs == 0 || hipMemcpy(ds, sys, zs, hipMemcpyHostToDevice) == hipSuccess);
+    if (ok) {
+        hipLaunchKernelGGL(alip::wave_helpers_kernel, dim3(1), dim3(alip::WAVE), 0, 0, di, nsets, ds, nsys, dout, dg);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+             (zo == 0 || hipMemcpy(out, dout, zo, hipMemcpyDeviceToHost) == hipSuccess) &&
+             (zg == 0 || hipMemcpy(gj_out, dg, zg, hipMemcpyDeviceToHost) == hipSuccess);
+    }
+    hipFree(d);
+    return ok ? alip::WH_SET : -1;
+}
 
 const char* alipmpc_build_id(void)
 {

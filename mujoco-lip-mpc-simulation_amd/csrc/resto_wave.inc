@@ -161,8 +161,7 @@ __device__ __forceinline__ int resto_wave(int wv, R fth0, R fph0, R fth1, R fph1
                 const R d1 = sr[q] - cl[q], d2_ = cu[q] - sr[q];
                 lso += llog(isfinite(cl[q]) ? (isfinite(cu[q]) ? d1 * d2_ : d1) : (isfinite(cu[q]) ? d2_ : R(1.0)));
             }
-            tho = wsum(tho);
-            lso = wsum(lso);
+            wsum_pair(tho, lso);
             const R fo = obj_sum<N, RPL>(cr, mr4);
             const R pho = fo - mu_o * lso;
             bool acc = isfinite(pho) && tho <= R(0.9) * theta_R;
@@ -284,12 +283,9 @@ __device__ __forceinline__ int resto_wave(int wv, R fth0, R fph0, R fth1, R fph1
                 }
             }
         }
-        nz = wsum(nz);
-        ny = wsum(ny);
-        dual = wmax(dual);
-        prim = wmax(prim);
-        whi = wmax(whi);
-        wlo = wmin(wlo);
+        wsum_pair(nz, ny);
+        wmax_pair(dual, prim);
+        wmaxmin_pair(whi, wlo);
         const R sd = uni(fmax(R(100), (nz + ny) / (R(n) + mal * R(3))) / R(100));
         const R sc = uni(fmax(R(100), nz / fmax(R(1), nbl)) / R(100));
         const R base = fmax(dual / sd, prim);
@@ -461,12 +457,12 @@ __device__ __forceinline__ int resto_wave(int wv, R fth0, R fph0, R fth1, R fph1
                 a[n] = rhs_l + R(0);
             };
             fill(R(0));
-            bool ok = gj_regs<n>(a, lane);
+            bool ok = gj_regs<n, R, gj_rb<RPL>>(a, lane);
             if (!ok) {
                 R dw = dw_last == R(0) ? R(1e-4) : fmax(R(1e-20), dw_last / R(3));
                 for (;;) {
                     fill(dw);
-                    if (gj_regs<n>(a, lane)) {
+                    if (gj_regs<n, R, gj_rb<RPL>>(a, lane)) {
                         ok = true;
                         break;
                     }
@@ -532,8 +528,12 @@ __device__ __forceinline__ int resto_wave(int wv, R fth0, R fph0, R fth1, R fph1
         // ---- dV = G dx; the rows' steps
         {
             R v = R(0);
+            if constexpr (dp_rows<n, NG, R>) {   // (as the regular loop)
+                v = gdp_rows<n, NCP>(G, xv, lane < NG ? lane : 0);
+            } else {
 #pragma unroll
-            for (int j = 0; j < n; ++j) v += G[(lane < NG ? lane : 0) * NCP + j] * bcast(xv, j);
+                for (int j = 0; j < n; ++j) v += G[(lane < NG ? lane : 0) * NCP + j] * bcast(xv, j);
+            }
             if (lane < NG) w.dV[lane] = v;
         }
         wave_sync();
@@ -582,10 +582,9 @@ __device__ __forceinline__ int resto_wave(int wv, R fth0, R fph0, R fth1, R fph1
         const R ex = lane < n ? xc - xR : R(0);
         lin += R(0.5) * zeta * d2 * ex * ex;
         gpn += zeta * d2 * ex * xv;
-        ap = wmin(ap);
-        az = wmin(az);
-        theta = wsum(theta);
-        const R gphi = wsum(gpn);
+        wmin_pair(ap, az);
+        wsum_pair(theta, gpn);
+        const R gphi = gpn;
         const R phi = wsum(lin);   // rho sum(p + n) + zeta/2 |D (x - xR)|^2 - mu sum ln(p n dl du)
         R amin;
         if (gphi < R(0)) {
@@ -630,8 +629,7 @@ __device__ __forceinline__ int resto_wave(int wv, R fth0, R fph0, R fth1, R fph1
             }
             const R et = ex + al * dxl;
             lt += R(0.5) * zeta * d2 * et * et;
-            tht = wsum(tht);
-            lt = wsum(lt);
+            wsum_pair(tht, lt);
             const R pht = __ballot(bad) != 0ull ? R(INFINITY) : lt;
             bool ok = isfinite(pht) && tht < theta_max;
             if (ok) {
@@ -640,7 +638,12 @@ __device__ __forceinline__ int resto_wave(int wv, R fth0, R fph0, R fth1, R fph1
                 ok = __ballot(b0 || b1) == 0ull;
             }
             if (ok) {
-                const bool switching = gphi < R(0) && llog(al) + sph * llog(-gphi) > sth * llog(theta);
+                bool switching = false;
+                if (gphi < R(0)) {   // (the three logs in one evaluation, llog3)
+                    R lal, lgp, lth;
+                    llog3(al, -gphi, theta, lal, lgp, lth);
+                    switching = lal + sph * lgp > sth * lth;
+                }
                 if (switching && theta <= theta_min) {
                     if (pht <= phi + eta * al * gphi) {
                         accepted = true;

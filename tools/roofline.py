@@ -36,13 +36,44 @@ from collections import defaultdict
 SIMDS, XCDS = 1024, 8
 
 
-def counters(d, kern, skip=1):
+def split_members(rows, launches):
+    """A split launch whose dispatches are different kernels of the family (the lean phase 1 and the paired phase 2,
+    each with a grid of its own): the rows per kernel name, when the family has exactly one name per launch."""
+    names = sorted({r["Kernel_Name"] for r in rows})
+    if launches > 1 and len(names) == launches:
+        return [[r for r in rows if r["Kernel_Name"] == nm] for nm in names]
+    return None
+
+
+def counters(d, kern, skip=1, launches=1):
     """Per-dispatch means of the kernel's counters over the dispatches of the benchmarked batch: the largest grid of
-    the family (bench.py's latency probe and feasibility checks launch the same kernel on small grids)."""
+    the family (bench.py's latency probe and feasibility checks launch the same kernel on small grids).  With
+    launches > 1 and one kernel name per launch: the mean per launch over the members (each at its own largest grid,
+    its first dispatch skipped), so that launches x the result is the sum over one solve."""
     acc = defaultdict(list)
     meta = {}
     for f in sorted(glob.glob(os.path.join(d, "pmc_*", "pmc_counter_collection.csv"))):
         rows = [r for r in csv.DictReader(open(f)) if r["Kernel_Name"].startswith(kern)]
+        members = split_members(rows, launches)
+        if members:
+            tot = defaultdict(float)
+            for m in members:
+                g = max(int(r["Grid_Size"]) for r in m)
+                m = [r for r in m if int(r["Grid_Size"]) == g]
+                ids = sorted({int(r["Dispatch_Id"]) for r in m})[1:]
+                per = defaultdict(list)
+                for r in m:
+                    if int(r["Dispatch_Id"]) in ids:
+                        per[r["Counter_Name"]].append(float(r["Counter_Value"]))
+                        # (the lean phase 1 comes first by name: its registers and scratch describe the record)
+                        meta = meta or {k: r[k] for k in ("Grid_Size", "Workgroup_Size", "LDS_Block_Size",
+                                                           "Scratch_Size", "VGPR_Count", "Accum_VGPR_Count",
+                                                           "SGPR_Count")}
+                for k, v in per.items():
+                    tot[k] += sum(v) / len(v)
+            for k, v in tot.items():
+                acc[k].append(v / launches)
+            continue
         if rows:
             g = max(int(r["Grid_Size"]) for r in rows)
             rows = [r for r in rows if int(r["Grid_Size"]) == g]
@@ -61,9 +92,19 @@ def kernel_ms(d, kern, launches=1):
     restricted like counters() to the largest grid of the family; else the stats summary."""
     for f in glob.glob(os.path.join(d, "prof_kt", "*kernel_trace.csv")):
         rows = [r for r in csv.DictReader(open(f)) if r["Kernel_Name"].startswith(kern)]
+
+        def gs(r):
+            return int(r["Grid_Size_X"]) * int(r["Grid_Size_Y"]) * int(r["Grid_Size_Z"])
+        members = split_members(rows, launches)
+        if members:   # (one kernel per launch: the members' mean durations summed)
+            ms, n = 0.0, 0
+            for m in members:
+                g = max(gs(r) for r in m)
+                dur = [int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in m if gs(r) == g]
+                ms += sum(dur) / len(dur) * 1e-6
+                n += len(dur)
+            return ms, n
         if rows:
-            def gs(r):
-                return int(r["Grid_Size_X"]) * int(r["Grid_Size_Y"]) * int(r["Grid_Size_Z"])
             g = max(gs(r) for r in rows)
             dur = [int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in rows if gs(r) == g]
             return launches * sum(dur) / len(dur) * 1e-6, len(dur)
@@ -124,7 +165,7 @@ def main():
     kern = kern[:-1] if kern.endswith(">") else kern   # the family: solve_kernel<..., true/false> (launch form)
     # per-solve figures: counters of the launches of one solve summed (first solve = warmup, skipped)
     launches = int(bench["config"].get("launches_per_solve", 1))
-    c, meta = counters(a.dir, kern, skip=launches)
+    c, meta = counters(a.dir, kern, skip=launches, launches=launches)
     c = {k: v * launches for k, v in c.items()}
     ms, calls = kernel_ms(a.dir, kern, launches)
     its = rl["iters_per_launch"]
