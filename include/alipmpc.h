@@ -376,6 +376,63 @@ int32_t alipmpc_trace_len(const alipmpc_cfg* cfg);
 int alipmpc_trace_batch(void* handle, int64_t B, const double* x0, const double* u, double* trace,
                         void* hip_stream);
 
+/*
+ * Plan audit: per instance, how far the plan u violates its constraints and how close its dense CoM trace comes to
+ * the obstacles; per call, integer counts of both.  One kernel launch (one instance per 16 lanes), nothing but the
+ * outputs below is written.  No reference counterpart: the reference inspects traces by plotting (plot_data_cir.py)
+ * and its driver keeps only feasi != 2 (main_sim_mpc.py:118).
+ *   Inputs as alipmpc_solve_batch; u B x 5N is the plan to audit (a solve's u_out); status B (may be NULL) the
+ *   solve's status, used by the summary's cross table only.
+ *   metrics B x ALIPMPC_AUDIT_COLS (may be NULL):
+ *     0 viol        max over the active rows of max(cl - c, c - cu, 0) with c, cl, cu, row_active exactly those
+ *                   alipmpc_eval_batch returns at u (the reference's rows, f_en included; select_obs and the detour as
+ *                   configured); 0 when no row is violated.
+ *     1 clear       min over all N x alipmpc_trace_len rows of the plan's dense trace (alipmpc_trace_batch's rows) and
+ *                   over all valid obstacles — the nc[b] circles and ne[b] ellipses as passed (inflated as passed,
+ *                   NOT filtered by select_obs) — of the radial clearance; +inf without a valid obstacle.
+ *     2 clear_knot  the same minimum over the N + 1 knots only: knot k < N is row 0 of step k (x_k), knot N the last
+ *                   row of step N - 1 (x_N).
+ *     3 goal_1      | knot 1 - goal |  (the goal as passed, not the detour goal)
+ *     4 goal_N      | knot N - goal |
+ *   Radial clearance of a point p to an obstacle (cx, cy, a, b, phi) — a circle is a = b = r, phi = 0; the semi-axis
+ *   a = elp[2] lies along phi, the reference's h_elp convention: d = p - c, Q = ((dx cos phi + dy sin phi) / a)^2 +
+ *   ((-dx sin phi + dy cos phi) / b)^2, clearance = |d| (1 - 1 / sqrt(Q)), and -min(a, b) at |d| = 0: the signed
+ *   distance to the boundary along the ray from the centre (for a circle |d| - r), negative inside.
+ *   where B x ALIPMPC_AUDIT_WHERE int32 (may be NULL):
+ *     0 viol_row    padded row index of viol (the smallest among equal violations), -1 when viol == 0
+ *     1 clear_row   flat trace row k * alipmpc_trace_len + r of clear
+ *     2 clear_obs   obstacle slot of clear: circle j is j, ellipse j is nc_max + j; -1 (with clear_row = -1): no obstacle
+ *     Among exactly equal clearances the smallest (row, obs) in row-major order wins (rows 0 and 1 of a step are
+ *     the same point).
+ *   Non-finite input: if any of x0[b], goal[b], u[b] is not finite (a rollout's plans after the goal are NaN), the
+ *   five metrics are NaN, where is -1 and only summary[0], [1] count the instance.
+ *   summary alipmpc_audit_summary_len(n_edges) = 6 + (n_edges + 1) + 20 int64 words (may be NULL), ADDED to what the
+ *   buffer holds, so one buffer carried through the chunks of a sweep ends as the whole sweep's (integer counts:
+ *   independent of chunking and of execution order):
+ *     [0] instances  [1] non-finite  [2] viol <= viol_tol  [3] clear >= 0  [4] both  [5] clear < 0 <= clear_knot (an
+ *     incursion between touchdowns only); [6 + i], i = 0..n_edges: clearance histogram, bin i counts edges[i - 1] <=
+ *     clear < edges[i] (first bin open below, last open above, +inf in the last); then, only when status != NULL
+ *     (else left untouched), 20 words indexed cls * 4 + 2 (clear >= 0) + (viol <= viol_tol) with cls = 0, 1, 2, 3, 4
+ *     for status 0, 1, -1, 2, other.
+ *   edges: n_edges finite, strictly increasing values, ALWAYS a host pointer (copied into the launch).
+ * Host / device pointers as alipmpc_solve_batch (edges excepted).  Device pointers: asynchronous on the stream, one
+ * launch, no device allocation, no host synchronisation.  Host pointers: summary is staged in, added to, staged out.
+ * Every LIP handle, whatever its precision and program (the audit arithmetic is always fp64); DD:
+ * ALIPMPC_EUNSUPPORTED.  ALIPMPC_EINVAL: B < 0, n_edges outside [0, ALIPMPC_AUDIT_MAX_EDGES], edges not finite or not
+ * strictly increasing, viol_tol negative or not finite, u == NULL, metrics, where and summary all NULL.
+ */
+#define ALIPMPC_AUDIT_COLS 5
+#define ALIPMPC_AUDIT_WHERE 3
+#define ALIPMPC_AUDIT_MAX_EDGES 62
+int32_t alipmpc_audit_summary_len(int32_t n_edges);   /* ALIPMPC_EINVAL for n_edges outside [0, 62] */
+int alipmpc_audit_batch(void* handle, int64_t B,
+                        const double* x0, const double* goal, const int8_t* leg,
+                        const double* cir, const int32_t* nc, const double* elp, const int32_t* ne,
+                        const double* u, const int32_t* status,
+                        double* metrics, int32_t* where, double viol_tol,
+                        const double* edges, int32_t n_edges, int64_t* summary,
+                        void* hip_stream);
+
 /* Instances this handle's solve kernel holds resident on its device at once (solve_kernel: resident
  * workgroups x 4 waves, one instance per wave; lane_kernel: resident waves x instances per wave).  A wave-program
  * batch that fits these slots launches one wave per instance (as a split launch, see alipmpc_solve_launches); a

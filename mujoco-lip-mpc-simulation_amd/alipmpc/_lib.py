@@ -46,7 +46,7 @@ EXPORTS = ("alipmpc_default_cfg", "alipmpc_rows_per_step", "alipmpc_num_vars", "
            "alipmpc_solve_batch", "alipmpc_eval_batch", "alipmpc_rollout_batch", "alipmpc_closed_loop_batch",
            "alipmpc_closed_loop_dataset_batch", "alipmpc_trace_len",
            "alipmpc_trace_batch", "alipmpc_nominal_gait_batch", "alipmpc_solve_slots", "alipmpc_solve_launches", "alipmpc_lane_handoffs", "alipmpc_solve_program", "alipmpc_last_kernel_ms",
-           "alipmpc_build_id", "alipmpc_scenes_batch",
+           "alipmpc_build_id", "alipmpc_scenes_batch", "alipmpc_audit_summary_len", "alipmpc_audit_batch",
            "alipmpc_last_error", "alipmpc_destroy")
 
 _lib = None
@@ -125,6 +125,11 @@ def load(build_if_missing=True):
         L.alipmpc_scenes_batch.argtypes = [P, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32,
                                            ctypes.c_int32, ctypes.c_int64, ctypes.c_int32] + [P] * 9
         L.alipmpc_scenes_batch.restype = ctypes.c_int
+    if hasattr(L, "alipmpc_audit_batch"):   # (absent from older dev builds used for A/B timing)
+        L.alipmpc_audit_summary_len.argtypes = [ctypes.c_int32]
+        L.alipmpc_audit_summary_len.restype = ctypes.c_int32
+        L.alipmpc_audit_batch.argtypes = [P, ctypes.c_int64] + [P] * 11 + [ctypes.c_double, P, ctypes.c_int32, P, P]
+        L.alipmpc_audit_batch.restype = ctypes.c_int
     L.alipmpc_last_kernel_ms.argtypes = [P]
     L.alipmpc_last_kernel_ms.restype = ctypes.c_double
     L.alipmpc_last_error.argtypes = [P]
@@ -171,6 +176,20 @@ def num_vars(cfg):
 
 def trace_len(cfg):
     return int(load().alipmpc_trace_len(ctypes.byref(cfg)))
+
+
+def audit_summary_len(n_edges):
+    """Words of an audit summary with n_edges histogram edges: 6 + (n_edges + 1) + 20 (alipmpc_audit_summary_len)."""
+    n = int(load().alipmpc_audit_summary_len(int(n_edges)))
+    if n < 0:
+        raise ValueError(f"alipmpc_audit_summary_len({n_edges}) -> {_ERRORS.get(n, n)}")
+    return n
+
+
+def _edges_arg(edges):
+    """(host array kept alive by the caller, pointer or None, count) of the histogram edges: always a host pointer."""
+    e = np.ascontiguousarray(np.asarray(edges, np.float64).reshape(-1))
+    return e, (_ptr(e) if e.size else None), int(e.size)
 
 
 STREAM_NULL = ctypes.c_void_p(ctypes.c_size_t(-1).value)   # ALIPMPC_STREAM_NULL
@@ -427,6 +446,43 @@ class Solver:
         rc = self._L.alipmpc_trace_batch(self._h, B, _ptr(x0), _ptr(u), _ptr(out), None)
         self._check(rc, "alipmpc_trace_batch")
         return out
+
+    def audit(self, x0, goal, leg, cir, nc, elp=None, ne=None, u=None, status=None, edges=(), viol_tol=1e-4,
+              summary=None):
+        """Plan audit (alipmpc_audit_batch) from host arrays: u (B,5N) the plans (a solve's u), status (B,) optional.
+        Returns dict(metrics (B,5), where (B,3), summary (audit_summary_len(len(edges)),) int64) — columns and words
+        as alipmpc.audit.COLS / WHERE / SUMMARY_FIELDS (include/alipmpc.h).  The summary counts from zero, or is added
+        to a copy of `summary` when one is given (the buffer a chunked sweep carries along)."""
+        B, x0, goal, leg, cir, nc, elp, ne = self._inputs(x0, goal, leg, cir, nc, elp, ne)
+        u = None if u is None else np.ascontiguousarray(u, np.float64).reshape(B, self.n)
+        st = None if status is None else np.ascontiguousarray(np.broadcast_to(np.asarray(status), (B,)), np.int32)
+        e, ep, ne_ = _edges_arg(edges)
+        words = 6 + ne_ + 1 + 20
+        acc = np.zeros(words, np.int64) if summary is None else np.array(summary, np.int64).reshape(-1)
+        if acc.size != words:
+            raise ValueError(f"summary has {acc.size} words, {words} expected for {ne_} edges")
+        out = dict(metrics=np.zeros((B, 5)), where=np.zeros((B, 3), np.int32), summary=acc)
+        rc = self._L.alipmpc_audit_batch(self._h, B, _ptr(x0), _ptr(goal), _ptr(leg), _ptr(cir), _ptr(nc), _ptr(elp),
+                                         _ptr(ne), _ptr(u), _ptr(st), _ptr(out["metrics"]), _ptr(out["where"]),
+                                         float(viol_tol), ep, ne_, _ptr(out["summary"]), None)
+        self._check(rc, "alipmpc_audit_batch")
+        return out
+
+    def audit_device(self, inp, out, edges=(), viol_tol=1e-4, stream=None):
+        """Asynchronous plan audit on device tensors: inp as solve_device's plus u (B,5N) the plans and optionally
+        status (B,) int32; out any of metrics (B,5) float64, where (B,3) int32, summary (audit_summary_len(len(edges)),)
+        int64 — the summary is ADDED to, so one tensor carried through the chunks of a sweep ends as the sweep's.
+        edges is a host sequence (copied into the launch)."""
+        import torch
+        st = stream if stream is not None else torch.cuda.current_stream()
+        B = inp["x0"].shape[0]
+        e, ep, ne_ = _edges_arg(edges)
+        rc = self._L.alipmpc_audit_batch(
+            self._h, B, _ptr(inp["x0"]), _ptr(inp["goal"]), _ptr(inp["leg"]), _ptr(inp["cir"]), _ptr(inp["nc"]),
+            _ptr(inp.get("elp")), _ptr(inp.get("ne")), _ptr(inp.get("u")), _ptr(inp.get("status")),
+            _ptr(out.get("metrics")), _ptr(out.get("where")), float(viol_tol), ep, ne_, _ptr(out.get("summary")),
+            _stream_arg(st))
+        self._check(rc, "alipmpc_audit_batch")
 
     def scenes(self, B, seed=0, first=0, n_cir=None, n_elp=0, fields=0, max_candidates=0):
         """Monte-Carlo scenes first .. first + B - 1 of the counter-based stream (alipmpc_scenes_batch), generated

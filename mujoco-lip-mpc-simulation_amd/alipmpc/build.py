@@ -3,7 +3,7 @@
 The library is the product: there is no CPU execution path behind it.
 
 csrc/alipmpc.hip is compiled as 9 translation units in parallel — ALIP_PART=0 (host code, C ABI, rollout
-kernels, the scene generator of csrc/scenes.inc, the dataset rows of csrc/dataset.inc), ALIP_PART=1..6 (the solve/eval kernels of one horizon N each, fp64 and fp32) and ALIP_PART=7/8 (the
+kernels, the scene generator of csrc/scenes.inc, the dataset rows of csrc/dataset.inc, the plan audit of csrc/audit.inc), ALIP_PART=1..6 (the solve/eval kernels of one horizon N each, fp64 and fp32) and ALIP_PART=7/8 (the
 lane solver of csrc/lane_solve.inc, fp64 / fp32) — and linked into one shared library.  `ALIPMPC_SINGLE_TU=1` builds it as one TU instead (slower, same code).
 """
 import hashlib
@@ -22,6 +22,7 @@ MATH = os.path.join(ROOT, "csrc", "fastmath.inc")
 RESTO = os.path.join(ROOT, "csrc", "resto_wave.inc")
 SCN = os.path.join(ROOT, "csrc", "scenes.inc")
 DSET = os.path.join(ROOT, "csrc", "dataset.inc")
+AUD = os.path.join(ROOT, "csrc", "audit.inc")
 HDR = os.path.join(REPO, "include", "alipmpc.h")
 LIB = os.path.join(PKG, "libalipmpc.so")
 PARTS = range(0, 9)
@@ -40,7 +41,7 @@ def build_id(extra=(), src=None):
     and the extra flags.  Compiled into the library (alipmpc_build_id) so a counter record made with one build is
     never attached to a bench line of another (tools/roofline.py, bench.py)."""
     h = hashlib.sha256()
-    for p in (src or SRC, INC, MATH, RESTO, SCN, DSET, HDR):
+    for p in (src or SRC, INC, MATH, RESTO, SCN, DSET, AUD, HDR):
         with open(p, "rb") as fh:
             h.update(fh.read())
     h.update(" ".join([*ARCH, *FLAGS, *extra]).encode())
@@ -51,7 +52,7 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    return any(os.path.getmtime(p) > t for p in (SRC, INC, MATH, RESTO, SCN, DSET, HDR, __file__))
+    return any(os.path.getmtime(p) > t for p in (SRC, INC, MATH, RESTO, SCN, DSET, AUD, HDR, __file__))
 
 
 def _run(cmd, verbose):

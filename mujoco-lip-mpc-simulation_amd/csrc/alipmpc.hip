@@ -5457,6 +5457,7 @@ __global__ __launch_bounds__(WAVE) void wave_helpers_kernel(const double* in, in
 #if ALIP_PART_HOST
 #include "scenes.inc"   // counter-based scene generator (alipmpc_scenes_batch)
 #include "dataset.inc"  // row scan / compaction of alipmpc_closed_loop_dataset_batch
+#include "audit.inc"    // plan audit (alipmpc_audit_batch)
 
 // ================================================================================================
 // host side: constants, handle, C ABI
@@ -5474,6 +5475,7 @@ struct Handle {
     double* dEp = nullptr;
     double* dGu = nullptr;
     double* dEu = nullptr;
+    double* dau = nullptr;   // plan audit (audit.inc): trace matrices and the per-sample cosh / sinh table
     // lane solver (lane_solve.inc): constants and the compiled circle-slot count it runs with (-1: the
     // per-wave solve_kernel serves this configuration)
     double* dlk = nullptr;
@@ -5618,6 +5620,33 @@ void build_tables(const alipmpc_cfg& cfg, int NCPP, int NCPU, std::vector<double
             for (int c = 0; c < 3; ++c) Gp[(8 * k + 5 + c) * NCPP + 3 * k + c] = 1.0;
     }
     (void)np_;
+}
+
+// plan audit table (audit.inc, AU_TAB_*): the matrices alipmpc_trace_batch passes to trace_kernel and, per trace sample
+// t_i = i * 0.01, cosh(beta t_i), sinh(beta t_i) / beta, 1 - cosh(beta t_i)
+void audit_table(const alipmpc_cfg& cfg, std::vector<double>& tab)
+{
+    const int rows = alipmpc_trace_len(&cfg);
+    tab.assign((size_t)au_tab_doubles(rows), 0.0);
+    const double b = std::sqrt(cfg.g / cfg.H), dT = cfg.dt, ch = std::cosh(b * dT), sh = std::sinh(b * dT);
+    const double A[25] = {ch, 0, sh / b, 0, 0, 0, ch, 0, sh / b, 0, sh * b, 0, ch, 0, 0,
+                          0, sh * b, 0, ch, 0, 0, 0, 0, 0, 1};
+    const double Bm[15] = {1 - ch, 0, 0, 0, 1 - ch, 0, -sh * b, 0, 0, 0, -sh * b, 0, 0, 0, 1};
+    const double Dd = 5.0 * (ch - 1) * (ch - 1) + (sh * b) * (sh * b);
+    const double Ch = -5.0 * (ch - 1) / Dd, Sh = -sh * b / Dd;
+    const double W[15] = {Ch, 0, Sh, 0, 0, 0, Ch, 0, Sh, 0, 0, 0, 0, 0, 1};
+    double BWA[25];
+    std::memcpy(&tab[AU_TAB_A], A, sizeof(A));
+    std::memcpy(&tab[AU_TAB_W], W, sizeof(W));
+    mm(Bm, W, &tab[AU_TAB_MB], 5, 3, 5);
+    mm(&tab[AU_TAB_MB], A, BWA, 5, 5, 5);
+    for (int i = 0; i < 25; ++i) tab[AU_TAB_MA + i] = A[i] - BWA[i];
+    for (int i = 0; i + 1 < rows; ++i) {
+        const double t = i * 0.01, c = std::cosh(b * t), s = std::sinh(b * t);
+        tab[AU_TAB_S + 3 * i] = c;
+        tab[AU_TAB_S + 3 * i + 1] = s / b;
+        tab[AU_TAB_S + 3 * i + 2] = 1 - c;
+    }
 }
 
 // lane-solver constants (lane::LK_* slots): the ALIP step map per axis, W, the foothold sensitivities
@@ -6091,6 +6120,14 @@ int alipmpc_create(const alipmpc_cfg* cfg, int device, void** handle)
         !create_events(h)) {
         alipmpc_destroy(h);
         return ALIPMPC_EHIP;
+    }
+    if (cfg->variant != ALIPMPC_VARIANT_DD && alipmpc_trace_len(cfg) > 1) {
+        std::vector<double> au;
+        audit_table(h->cfg, au);
+        if (!up(&h->dau, au)) {
+            alipmpc_destroy(h);
+            return ALIPMPC_EHIP;
+        }
     }
     {
         double lk[alip::lane::LK_BUF];
@@ -6940,6 +6977,103 @@ int alipmpc_trace_batch(void* handle, int64_t B, const double* x0, const double*
     return ALIPMPC_OK;
 }
 
+int32_t alipmpc_audit_summary_len(int32_t n_edges)
+{
+    if (n_edges < 0 || n_edges > ALIPMPC_AUDIT_MAX_EDGES) return ALIPMPC_EINVAL;
+    return AU_HEAD + (n_edges + 1) + AU_CROSS;
+}
+
+int alipmpc_audit_batch(void* handle, int64_t B, const double* x0, const double* goal, const int8_t* leg,
+                        const double* cir, const int32_t* nc, const double* elp, const int32_t* ne, const double* u,
+                        const int32_t* status, double* metrics, int32_t* where, double viol_tol, const double* edges,
+                        int32_t n_edges, int64_t* summary, void* hip_stream)
+{
+    Handle* h = (Handle*)handle;
+    if (!h) return ALIPMPC_EINVAL;
+    const alipmpc_cfg& cf = h->cfg;
+    if (cf.variant == ALIPMPC_VARIANT_DD) return fail(h, ALIPMPC_EUNSUPPORTED, "audit: LIP variants only");
+    if (B < 0) return fail(h, ALIPMPC_EINVAL, "B < 0");
+    if (n_edges < 0 || n_edges > ALIPMPC_AUDIT_MAX_EDGES)
+        return fail(h, ALIPMPC_EINVAL, "audit: n_edges outside [0, ALIPMPC_AUDIT_MAX_EDGES]");
+    if (n_edges > 0 && !edges) return fail(h, ALIPMPC_EINVAL, "audit: edges is NULL");
+    for (int i = 0; i < n_edges; ++i)
+        if (!std::isfinite(edges[i]) || (i > 0 && !(edges[i] > edges[i - 1])))
+            return fail(h, ALIPMPC_EINVAL, "audit: edges must be finite and strictly increasing");
+    if (!std::isfinite(viol_tol) || viol_tol < 0) return fail(h, ALIPMPC_EINVAL, "audit: viol_tol must be finite and >= 0");
+    if (!u) return fail(h, ALIPMPC_EINVAL, "audit: u is NULL");
+    if (!metrics && !where && !summary) return fail(h, ALIPMPC_EINVAL, "audit: no output requested");
+    if (!x0 || !goal || !leg || !nc || (cf.nc_max > 0 && !cir) || (cf.ne_max > 0 && (!elp || !ne)))
+        return fail(h, ALIPMPC_EINVAL, "missing input pointer");
+    if (!h->dau) return fail(h, ALIPMPC_EUNSUPPORTED, "audit: the plan has no dense trace (dt <= 0)");
+    if (B == 0) return ALIPMPC_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int N = h->N, nu = 5 * N;
+    const size_t Bz = (size_t)B, ncm = (size_t)cf.nc_max, nem = (size_t)cf.ne_max;
+    const size_t nsum = (size_t)alipmpc_audit_summary_len(n_edges);
+    AuP A;
+    std::memset(&A, 0, sizeof(A));
+    A.kp = make_kp(h, B, false);
+    A.N = N;
+    A.rows = alipmpc_trace_len(&cf);
+    A.n_edges = n_edges;
+    A.has_status = status != nullptr;
+    A.tab = h->dau;
+    A.viol_tol = viol_tol;
+    for (int i = 0; i < n_edges; ++i) A.edges[i] = edges[i];
+    KP& P = A.kp;
+    hipStream_t st = stream_of(h, hip_stream);
+    const bool host = hip_stream == nullptr;
+    if (host) {
+        const size_t bytes = Bz * 8 * (5 + 2 + 3 * ncm + 5 * nem + nu + ALIPMPC_AUDIT_COLS) +
+                             Bz * (1 + 4 + 4 + 4 + 4 * ALIPMPC_AUDIT_WHERE) + nsum * 8 + 13 * 256;
+        if (int rc = ensure_stage(h, bytes)) return rc;
+        Carver cv{(char*)h->stage};
+        double* dx = cv.take<double>(Bz * 5);
+        double* dg = cv.take<double>(Bz * 2);
+        double* dc = cv.take<double>(Bz * 3 * ncm);
+        double* de = cv.take<double>(Bz * 5 * nem);
+        double* du = cv.take<double>(Bz * nu);
+        double* dm = cv.take<double>(Bz * ALIPMPC_AUDIT_COLS);
+        int64_t* ds = cv.take<int64_t>(nsum);
+        int32_t* dnc = cv.take<int32_t>(Bz);
+        int32_t* dne = cv.take<int32_t>(Bz);
+        int32_t* dst = cv.take<int32_t>(Bz);
+        int32_t* dw = cv.take<int32_t>(Bz * ALIPMPC_AUDIT_WHERE);
+        int8_t* dl = cv.take<int8_t>(Bz);
+        auto h2d = [&](void* d, const void* s, size_t n) { return hipMemcpyAsync(d, s, n, hipMemcpyHostToDevice, st); };
+        HIPCHK(h, h2d(dx, x0, Bz * 5 * 8));
+        HIPCHK(h, h2d(dg, goal, Bz * 2 * 8));
+        HIPCHK(h, h2d(dl, leg, Bz));
+        if (ncm) HIPCHK(h, h2d(dc, cir, Bz * 3 * ncm * 8));
+        HIPCHK(h, h2d(dnc, nc, Bz * 4));
+        if (nem) {
+            HIPCHK(h, h2d(de, elp, Bz * 5 * nem * 8));
+            HIPCHK(h, h2d(dne, ne, Bz * 4));
+        }
+        HIPCHK(h, h2d(du, u, Bz * nu * 8));
+        if (status) HIPCHK(h, h2d(dst, status, Bz * 4));
+        if (summary) HIPCHK(h, h2d(ds, summary, nsum * 8));
+        P.x0 = dx; P.goal = dg; P.leg = dl; P.cir = dc; P.nc = dnc;
+        P.elp = nem ? de : nullptr; P.ne = nem ? dne : nullptr; P.u0 = du;
+        A.status = status ? dst : nullptr;
+        A.metrics = metrics ? dm : nullptr;
+        A.where = where ? dw : nullptr;
+        A.summary = summary ? (unsigned long long*)ds : nullptr;
+    } else {
+        P.x0 = x0; P.goal = goal; P.leg = leg; P.cir = cir; P.nc = nc;
+        P.elp = nem ? elp : nullptr; P.ne = nem ? ne : nullptr; P.u0 = u;
+        A.status = status; A.metrics = metrics; A.where = where; A.summary = (unsigned long long*)summary;
+    }
+    HIPCHK(h, launch_audit(N, A, st));
+    if (host) {
+        if (metrics) HIPCHK(h, hipMemcpyAsync(metrics, A.metrics, Bz * ALIPMPC_AUDIT_COLS * 8, hipMemcpyDeviceToHost, st));
+        if (where) HIPCHK(h, hipMemcpyAsync(where, A.where, Bz * ALIPMPC_AUDIT_WHERE * 4, hipMemcpyDeviceToHost, st));
+        if (summary) HIPCHK(h, hipMemcpyAsync(summary, A.summary, nsum * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipStreamSynchronize(st));
+    }
+    return ALIPMPC_OK;
+}
+
 int alipmpc_nominal_gait_batch(void* handle, int64_t B, double vx_max, const double* x, const int8_t* leg,
                                const double* vel_des_in, double* vel_des, double* foot, void* hip_stream)
 {
@@ -7209,7 +7343,7 @@ void alipmpc_destroy(void* handle)
     if (!h) return;
     hipSetDevice(h->device);
     if (h->own) hipStreamSynchronize(h->own);
-    for (double* d : {h->dGp, h->dEp, h->dGu, h->dEu})
+    for (double* d : {h->dGp, h->dEp, h->dGu, h->dEu, h->dau})
         if (d) (void)hipFree(d);
     if (h->dq) hipFree(h->dq);
     if (h->dlk) hipFree(h->dlk);

@@ -11,6 +11,9 @@ time of scenes.make_batch_vec for one 16,384-instance chunk.
   timeout 600 python tools/mc_sweep.py                      # cfg5's shape
   timeout 600 python tools/mc_sweep.py --scenes 65536 --n-cir 5 --n-elp 5 --horizon 5 --fields 4096   # dense mix
 With --n-elp > 0 the solve is the fp64 wave program (the lane program takes circles only).
+--audit adds the plan audit (alipmpc_audit_batch) of every chunk's solutions on the same device buffers: one summary
+buffer is carried through all chunks and read once at the end; the JSON line gains "audit" (constraint violation x
+dense-trace clearance counts, the clearance histogram over --edges, the table by status class) and "audit_ms".
 """
 import argparse
 import json
@@ -40,6 +43,10 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--gen-only", action="store_true", help="generate only (no solve, no feasible fraction)")
     ap.add_argument("--no-host", action="store_true", help="skip the host generator comparison")
+    ap.add_argument("--audit", action="store_true", help="audit every plan on the device (violation, trace clearance)")
+    ap.add_argument("--edges", default="-0.2,-0.1,-0.05,0,0.05,0.1,0.2,0.4",
+                    help="clearance histogram edges in metres for --audit (comma-separated, increasing)")
+    ap.add_argument("--viol-tol", type=float, default=1e-4, help="violation tolerance for --audit")
     a = ap.parse_args()
 
     import torch
@@ -68,6 +75,11 @@ def main():
     gen_kw = dict(seed=a.seed, n_cir=a.n_cir, n_elp=a.n_elp, fields=a.fields)
     st = torch.cuda.current_stream()
     infeasible = torch.zeros((), dtype=torch.int64, device=dev)
+    do_audit = a.audit and not a.gen_only
+    if do_audit:
+        from alipmpc import audit
+        edges = [float(v) for v in a.edges.split(",") if v.strip()]
+        asum = torch.zeros(alipmpc.audit_summary_len(len(edges)), dtype=torch.int64, device=dev)
 
     def views(d, n):
         return d if n == C else {k: v[:n] for k, v in d.items()}
@@ -81,14 +93,21 @@ def main():
             s.solve_device(i, o, stream=st)
             ev[2].record(st)
             infeasible.add_((o["status"] == 2).sum())
+            if do_audit:
+                ev[3].record(st)
+                s.audit_device(dict(i, u=o["u"], status=o["status"]), dict(summary=asum), edges=edges,
+                               viol_tol=a.viol_tol, stream=st)
+                ev[4].record(st)
 
     def events():
-        return [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        return [torch.cuda.Event(enable_timing=True) for _ in range(5)]
 
     # warm-up (code-object load, first-launch set-up): the first chunk's range, not timed
     chunk(a.first, min(C, count), events())
     torch.cuda.synchronize()
     infeasible.zero_()
+    if do_audit:
+        asum.zero_()
     evs = []
     t0 = time.perf_counter()
     for lo in range(a.first, a.first + count, C):
@@ -106,6 +125,10 @@ def main():
         rec.update(program=s.solve_program(), solve_ms=round(solve_ms, 4),
                    solves_per_s=round(count / (solve_ms * 1e-3), 1), gen_over_solve=round(gen_ms / solve_ms, 5),
                    feasible_fraction=round(1.0 - infeasible.item() / count, 6))
+    if do_audit:
+        audit_ms = sum(e[3].elapsed_time(e[4]) for e in evs)
+        rec.update(audit_ms=round(audit_ms, 4), audit_over_solve=round(audit_ms / solve_ms, 5),
+                   audit=audit.describe(asum.cpu().numpy(), len(edges), edges))
     if not a.no_host:
         t0 = time.perf_counter()
         scenes.make_batch_vec(HOST_CHUNK, seed=a.seed, n_cir=a.n_cir, n_elp=a.n_elp, N=a.horizon,
