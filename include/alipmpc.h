@@ -51,6 +51,14 @@
  *   select_obs (modi) compacts the kept obstacles, in input order, into the first slots; unused slots
  *   are inactive (row_active = 0, cl = -inf, cu = +inf, value/Jacobian rows = 0).  Dropping the
  *   inactive rows gives exactly the reference's row order.
+ *   The lane program (cfg.program = ALIPMPC_PROGRAM_LANE) keeps the solve's own rows in this slot order without
+ *   compacting them (an unselected obstacle's slot stays in place, inactive).  Its shapes, all N = 3:
+ *     circles only (ne_max = 0), nc_max <= 6, modi / sig_step: circle slots [cx, cy, r^2];
+ *     circles and ellipses (ne_max >= 1), nc_max + ne_max <= 5, modi: 5 quadratic-form slots — slot j < nc_max is
+ *     circle j, slot nc_max + j is ellipse j, each (ox, oy, qa, qb, qc, k) with h(p) = qa dx^2 + qb dx dy + qc dy^2 - k
+ *     (an ellipse [cx, cy, a, b, phi]: qa = (b cos)^2 + (a sin)^2, qb = 2 cos sin (b^2 - a^2), qc = (b sin)^2 +
+ *     (a cos)^2, k = (a b)^2; a circle: qa = qc = 1, qb = 0, k = r^2).  A sixth slot would cost the kernel its fourth
+ *     wave per compute unit, so nc_max = 6 stays circles only.
  */
 #ifndef ALIPMPC_H
 #define ALIPMPC_H
@@ -122,8 +130,10 @@ typedef struct alipmpc_cfg {
     int32_t program;    /* device program (no reference counterpart; the arithmetic of the interior point is the
                            same in both): ALIPMPC_PROGRAM_WAVE — one instance per wavefront (solve_kernel,
                            latency-optimised: small batches); ALIPMPC_PROGRAM_LANE — one instance per lane
-                           (lane_kernel, throughput-optimised: batches of 10^5+ instances; N = 3 with circles only,
-                           modi / sig_step, otherwise alipmpc_create returns ALIPMPC_EUNSUPPORTED).  A per-handle
+                           (lane_kernel, throughput-optimised: batches of 10^5+ instances; N = 3 with either
+                           ne_max = 0, nc_max <= 6, modi / sig_step, or ne_max >= 1, nc_max + ne_max <= 5, modi — the
+                           obstacle-form build, circles and ellipses; otherwise alipmpc_create returns
+                           ALIPMPC_EUNSUPPORTED: other N, DD, sig_step with ellipse slots, more slots).  A per-handle
                            choice, never a function of B: an instance's result does not depend on its batch. */
     int32_t goal_singular; /* a planned state exactly on the goal, where the target heading atan2(g - p) has 0 / 0
                            derivatives (the reference's cal_dtar_ang_du, MPC_LIP_modi.py:650-655, returns NaN there):
@@ -467,8 +477,11 @@ int alipmpc_lane_handoffs(void* handle, void* hip_stream, int64_t* count);
 /* The device program this handle's solves run (cfg.program): "solve_kernel<N,rows/4,type>" (one instance per
  * wavefront; launched as one wave per instance when the batch fits alipmpc_solve_slots, as the persistent
  * work queue otherwise — the same bits per instance either way), "lane_kernel<N,circle slots,modi,type>" (one
- * instance per lane) or "dd_solve_kernel<N,row groups>".  No reference counterpart.  The string is owned by
- * the library. */
+ * instance per lane, circles only: the compiled slot count 0, 5 or 6 serving cfg.nc_max),
+ * "lane_kernel<3,5,true,Form<type>>" (one instance per lane, the obstacle-form build: 5 form slots serving every
+ * cfg.nc_max + cfg.ne_max <= 5 with cfg.ne_max >= 1, modi; a profiler prints that kernel as
+ * lane_kernel<3, 5, true, alip::lane::Form<type>>) or "dd_solve_kernel<N,row groups>".  No reference counterpart.  The
+ * string is owned by the library. */
 const char* alipmpc_solve_program(void* handle);
 
 /* Duration in milliseconds of the most recent solve kernel launch on this handle, measured with HIP

@@ -5280,12 +5280,14 @@ ALIP_LAUNCHERS(5)
 ALIP_LAUNCHERS(6)
 #endif
 
-// lane solver (lane_solve.inc): N = 3, circles only, NC = compiled circle slots (>= cfg.nc_max).  A persistent
+// lane solver (lane_solve.inc): N = 3, NC = compiled circle slots (>= cfg.nc_max), or (nct = LANE_FORM5, modi) the
+// form build's 5 obstacle-form slots (circles and ellipses, >= cfg.nc_max + cfg.ne_max).  A persistent
 // grid of at most the resident one-wave workgroups; each lane takes instances from the launch's work queue.
-template <int N, int NC, bool MODI, class R>
+constexpr int LANE_FORM5 = 100 + 5;
+template <int N, int NC, bool MODI, class R, bool FM = false>
 void launch_lane_t(const KP& P, hipStream_t st, unsigned* res_out)
 {
-    auto kern = lane_kernel<N, NC, MODI, R>;
+    auto kern = lane_kernel<N, NC, MODI, typename std::conditional<FM, lane::Form<R>, R>::type>;
     const unsigned res = resident_blocks((const void*)kern, 0, WAVE);
     if (res_out) {
         *res_out = res;
@@ -5303,6 +5305,7 @@ hipError_t launch_lane_r(int nct, bool modi, const KP& P, hipStream_t st, unsign
         if (nct == 0) launch_lane_t<3, 0, true, R>(P, st, res_out);
         else if (nct == 5) launch_lane_t<3, 5, true, R>(P, st, res_out);
         else if (nct == 6) launch_lane_t<3, 6, true, R>(P, st, res_out);
+        else if (nct == LANE_FORM5) launch_lane_t<3, 5, true, R, true>(P, st, res_out);
         else return hipErrorInvalidValue;
     } else {
         if (nct == 0) launch_lane_t<3, 0, false, R>(P, st, res_out);
@@ -5728,11 +5731,15 @@ void lane_constants(const alipmpc_cfg& cfg, double* lk)
     }
 }
 
-// the compiled lane-solver instance (circle slots) serving cfg, or -1 when none does: N = 3 with circles
-// only (<= 6 slots), modi / sig_step (BASELINE cfg1/2/4/5 shapes)
+// the compiled lane-solver instance serving cfg, or -1 when none does: N = 3 with circles only (<= 6 circle slots),
+// modi / sig_step (BASELINE cfg1/2/4/5 shapes); with ellipses (ne_max >= 1) modi's form build, nc_max + ne_max <= 5
+// (LANE_FORM5: its 157 LDS entries per lane keep four waves on a CU, a sixth slot would not — lane_solve.inc)
 int lane_slots_for(const alipmpc_cfg& c)
 {
-    if (c.variant == ALIPMPC_VARIANT_DD || c.N != 3 || c.ne_max != 0 || c.nc_max > 6) return -1;
+    if (c.variant == ALIPMPC_VARIANT_DD || c.N != 3) return -1;
+    if (c.ne_max != 0)
+        return c.variant == ALIPMPC_VARIANT_MODI && c.ne_max >= 1 && c.nc_max + c.ne_max <= 5 ? LANE_FORM5 : -1;
+    if (c.nc_max > 6) return -1;
     return c.nc_max == 0 ? 0 : c.nc_max <= 5 ? 5 : 6;
 }
 
@@ -7328,6 +7335,8 @@ const char* alipmpc_solve_program(void* handle)
     if (c.variant == ALIPMPC_VARIANT_DD) {
         const int rpl = h->mo4 / WAVE;
         std::snprintf(buf, sizeof(buf), "dd_solve_kernel<%d,%d>", h->N, rpl);
+    } else if (h->lane_nct == LANE_FORM5) {
+        std::snprintf(buf, sizeof(buf), "lane_kernel<%d,5,true,Form<%s>>", h->N, r);
     } else if (h->lane_nct >= 0) {
         std::snprintf(buf, sizeof(buf), "lane_kernel<%d,%d,%s,%s>", h->N, h->lane_nct,
                       c.variant == ALIPMPC_VARIANT_MODI ? "true" : "false", r);

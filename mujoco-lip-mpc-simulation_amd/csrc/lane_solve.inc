@@ -20,6 +20,9 @@
 //   [vbx, vby, circle slot 0..NC-1, leg, dtheta, (modi) vbx + s dth <= hi, vbx - s dth <= hi]
 // Unselected circle slots stay in place and are inactive (no bounds, no multipliers): the compacted row
 // order of the reference differs only in the order of the sums.
+// The form build (FM: lane_kernel<N, NS, true, Form<R>>, modi only) has NS obstacle-form slots in the circle slots'
+// place: slot j < cfg.nc_max is circle j, slot cfg.nc_max + j is ellipse j (the padded row order of alipmpc.h), each a
+// quadratic form (ox, oy, qa, qb, qc, k) with the D-CBF row of MPC_LIP_modi.py:598-617 (h_elp; kind FRM below).
 // Decision: footholds p = [fx_k, fy_k, dth_k]_k (n = 3N) as in solve_kernel (DESIGN.md §2 item 2); the
 // x/y/theta channels of the ALIP step map are decoupled, so d x_k / d p_j is two scalars per axis
 // (SP/SV below) and a 1 for theta: every Jacobian row is built from <= 4 state-space coefficients.
@@ -58,7 +61,9 @@ enum {
 };
 constexpr int LK_BUF = 64;   // lane-constant buffer (fp64 and fp32 copies)
 
-enum { VBX = 0, VBY, CIR, LEG, DTH, FEN, FENM };
+enum { VBX = 0, VBY, CIR, LEG, DTH, FEN, FENM, FRM };
+template <int KD>
+constexpr bool is_obs() { return KD == CIR || KD == FRM; }   // an obstacle slot's row: circle or quadratic form
 enum { GPX = 0, GPY, GVX, GVY, GTH, GFX, GFY, GFT, GNONE };
 
 
@@ -90,6 +95,14 @@ struct Shape {
     static constexpr int ZUS = MODI ? 6 : 4;               // rows with an upper bound per step (all but circles)
     static constexpr int NZL = N * ZLS, NZU = N * ZUS;
 };
+
+// the kernel's arithmetic argument: R, or Form<R> for the obstacle-form build of the same arithmetic
+template <class R>
+struct Form {};
+template <class RT>
+struct Real { using type = RT; static constexpr bool form = false; };
+template <class R>
+struct Real<Form<R>> { using type = R; static constexpr bool form = true; };
 
 template <int K_>
 using KindT = std::integral_constant<int, K_>;
@@ -138,12 +151,13 @@ constexpr int lanes_of() { return sizeof(R) == 8 ? 32 : 64; }
 
 // per-wave LDS, [entry][lane] (each access conflict-free).  Entries: s (M rows), dS (M), z_l (rows with a
 // lower bound), z_u (rows with an upper bound), circle forms ox / oy / r^2 (NC each), filter theta / phi.
+// OE entries per obstacle slot: 3 (circles) or 6 (the form build: ox / oy / k, then qa / qb / qc).
 // The lane base is laundered at every pass so loads are not CSE'd across passes into long-lived registers.
-template <class R, int N, int NC, bool MODI, int L>
+template <class R, int N, int NC, bool MODI, int L, int OE = 3>
 struct Lds {
     using S = Shape<N, NC, MODI>;
     // (fp32: the filter's barrier-function values are fp64, kept as hi / lo fp32 pairs: FCAP more entries)
-    static constexpr int ENT = 2 * S::M + S::NZL + S::NZU + 3 * NC + 2 * FCAP + (sizeof(R) == 4 && !ALIP_LANE_M32 ? FCAP : 0);
+    static constexpr int ENT = 2 * S::M + S::NZL + S::NZU + OE * NC + 2 * FCAP + (sizeof(R) == 4 && !ALIP_LANE_M32 ? FCAP : 0);
     // an LDS-address-space pointer: a generic one (which the laundering would leave the compiler with)
     // turns every access into a FLAT instruction on the vector-memory path
     typedef __attribute__((address_space(3))) R lr;
@@ -156,9 +170,13 @@ struct Lds {
     __device__ __forceinline__ lr& ox(int j) const { return b[(2 * S::M + S::NZL + S::NZU + j) * L]; }
     __device__ __forceinline__ lr& oy(int j) const { return b[(2 * S::M + S::NZL + S::NZU + NC + j) * L]; }
     __device__ __forceinline__ lr& orr(int j) const { return b[(2 * S::M + S::NZL + S::NZU + 2 * NC + j) * L]; }
-    __device__ __forceinline__ lr& fth(int e) const { return b[(2 * S::M + S::NZL + S::NZU + 3 * NC + e) * L]; }
-    __device__ __forceinline__ lr& fph(int e) const { return b[(2 * S::M + S::NZL + S::NZU + 3 * NC + FCAP + e) * L]; }
-    __device__ __forceinline__ lr& fpl(int e) const { return b[(2 * S::M + S::NZL + S::NZU + 3 * NC + 2 * FCAP + e) * L]; }
+    // (OE = 6: orr holds the form's k; circles in a form slot have qa = qc = 1, qb = 0, k = r^2)
+    __device__ __forceinline__ lr& qa(int j) const { return b[(2 * S::M + S::NZL + S::NZU + 3 * NC + j) * L]; }
+    __device__ __forceinline__ lr& qb(int j) const { return b[(2 * S::M + S::NZL + S::NZU + 4 * NC + j) * L]; }
+    __device__ __forceinline__ lr& qc(int j) const { return b[(2 * S::M + S::NZL + S::NZU + 5 * NC + j) * L]; }
+    __device__ __forceinline__ lr& fth(int e) const { return b[(2 * S::M + S::NZL + S::NZU + OE * NC + e) * L]; }
+    __device__ __forceinline__ lr& fph(int e) const { return b[(2 * S::M + S::NZL + S::NZU + OE * NC + FCAP + e) * L]; }
+    __device__ __forceinline__ lr& fpl(int e) const { return b[(2 * S::M + S::NZL + S::NZU + OE * NC + 2 * FCAP + e) * L]; }
     // a filter entry's barrier-function value (merit_t: with ALIP_LANE_M32=0 the fp32 build keeps fp64 hi / lo pairs)
     __device__ __forceinline__ merit_t<R> fphi(int e) const
     {
@@ -185,7 +203,7 @@ template <class R>
 struct Inst {
     R x0[5];
     R gx, gy;    // goal after the detour heuristic
-    int act;     // bit j: circle slot j selected
+    int act;     // bit j: circle (form build: obstacle) slot j selected
     int legp;    // od_ev > 0
 };
 
@@ -405,6 +423,32 @@ __device__ __forceinline__ R row_eval(const LK<R>& C, const Step<R>& st, R ox, R
     }
 }
 
+// the form build's obstacle row (kind FRM): h(p) = qa dx^2 + qb dx dy + qc dy^2 - k, d = p - (ox, oy), and the D-CBF
+// row c = h(x_{k+1}) + (gamma - 1) h(x_k) (MPC_LIP_modi.py:598-617), coefficients on the CIR generators
+template <class R>
+__device__ __forceinline__ R form_eval(const LK<R>& C, const Step<R>& st, R ox, R oy, R qa, R qb, R qc, R kk, R (&cf)[4])
+{
+    const R gm1 = C[LK_GM1];
+    const R x1 = st.x1[0] - ox, y1 = st.x1[1] - oy, x0 = st.x0[0] - ox, y0 = st.x0[1] - oy;
+    cf[0] = fma(R(2) * qa, x1, qb * y1);
+    cf[1] = fma(R(2) * qc, y1, qb * x1);
+    cf[2] = gm1 * fma(R(2) * qa, x0, qb * y0);
+    cf[3] = gm1 * fma(R(2) * qc, y0, qb * x0);
+    const R h1 = fma(qa * x1, x1, fma(qb * x1, y1, qc * y1 * y1)) - kk;
+    const R h0 = fma(qa * x0, x0, fma(qb * x0, y0, qc * y0 * y0)) - kk;
+    return fma(gm1, h0, h1);
+}
+// a row's value and coefficients with its obstacle slot's entries (slot j) read from LDS where they are used
+template <int KD, class R, class LD>
+__device__ __forceinline__ R row_value(const LK<R>& C, const Step<R>& st, const LD& ld, int j, R (&cf)[4])
+{
+    if constexpr (KD == FRM)
+        return form_eval<R>(C, st, ld.ox(j), ld.oy(j), ld.qa(j), ld.qb(j), ld.qc(j), ld.orr(j), cf);
+    else
+        return row_eval<KD, R>(C, st, KD == CIR ? ld.ox(j) : R(0), KD == CIR ? ld.oy(j) : R(0),
+                               KD == CIR ? ld.orr(j) : R(0), cf);
+}
+
 // relaxed (IPOPT bound_relax_factor 1e-8, as the oracle) or original bounds of a row of kind KD at step k
 template <int KD, class R>
 __device__ __forceinline__ void row_bounds(const LK<R>& C, int legp, int k, R& cl, R& cu, bool orig = false)
@@ -416,7 +460,7 @@ __device__ __forceinline__ void row_bounds(const LK<R>& C, int legp, int k, R& c
     } else if constexpr (KD == VBY) {
         cl = pos ? C[LK_VYLP + o] : C[LK_VYLN + o];
         cu = pos ? C[LK_VYUP + o] : C[LK_VYUN + o];
-    } else if constexpr (KD == CIR) {
+    } else if constexpr (is_obs<KD>()) {
         cl = orig ? R(0) : C[LK_CIRL]; cu = R(INFINITY);
     } else if constexpr (KD == LEG) {
         cl = orig ? R(0) : C[LK_LEGL]; cu = orig ? C[LK_OLEGU] : C[LK_LEGU];
@@ -429,16 +473,16 @@ __device__ __forceinline__ void row_bounds(const LK<R>& C, int legp, int k, R& c
 template <int KD>
 constexpr bool has_lo() { return KD != FEN && KD != FENM; }
 template <int KD>
-constexpr bool has_up() { return KD != CIR; }
+constexpr bool has_up() { return !is_obs<KD>(); }
 
-// every row of step k: f(KindT<kind>, l (row within the step), j (circle slot)); circle rows in a loop
-template <int NC, bool MODI, class F>
+// every row of step k: f(KindT<kind>, l (row within the step), j (obstacle slot)); circle / form rows in a loop
+template <int NC, bool MODI, bool FM = false, class F>
 __device__ __forceinline__ void step_rows(F&& f)
 {
     f(KindT<VBX>(), 0, 0);
     f(KindT<VBY>(), 1, 0);
 #pragma unroll 1
-    for (int j = 0; j < NC; ++j) f(KindT<CIR>(), 2 + j, j);
+    for (int j = 0; j < NC; ++j) f(KindT<FM ? FRM : CIR>(), 2 + j, j);
     f(KindT<LEG>(), 2 + NC, 0);
     f(KindT<DTH>(), 3 + NC, 0);
     if constexpr (MODI) {
@@ -532,20 +576,30 @@ __device__ __forceinline__ void ksym(RK (&K)[n][n], int a, int b, RK v)
 // applied to the slacks and multipliers in the same pass that assembles K, the right-hand side and the
 // error terms; then the barrier update, the factorisation and one pass for dS and the step bounds), phase 2
 // (one line-search trial: one evaluation and one pass).  A rejected trial keeps the lane in phase 2.
-template <int N, int NC, bool MODI, class R>
+//
+// RT: R itself (NC circle slots), or lane::Form<R> — the form build: NC obstacle-form slots (circles and ellipses,
+// modi) in their place, a kernel of its own name (lane_kernel<N, NS, true, alip::lane::Form<R>>).  Its entry count per
+// lane at N = 3: 2 * 3 * (6 + NS) + 3 * (4 + NS) + 18 + 6 * NS + 16 = 157 at NS = 5; four one-wave workgroups per CU
+// need <= 160 entries (160 x 256 B x 4 = the CU's 160 KB), NS = 6 has 172.
+template <int N, int NC, bool MODI, class RT>
 __global__ __launch_bounds__(64, 1) void lane_kernel(KP P)
 {
     using namespace lane;
+    using R = typename Real<RT>::type;
+    constexpr bool FM = Real<RT>::form;
+    static_assert(!FM || MODI, "the form build is modi's (sig_step has no ellipse rows)");
     using RK = double;
     using S = Shape<N, NC, MODI>;
     constexpr int n = S::n, RPS = S::RPS;
     constexpr int L = lanes_of<R>();
     constexpr int NKL = n * (n + 1) / 2;
     constexpr int U_NONE = 0, U_INIT = 1, U_ACC = 2, U_REST = 3;   // pending update kinds
-    __shared__ R smem_[Lds<R, N, NC, MODI, L>::ENT * L];
+    using LD = Lds<R, N, NC, MODI, L, FM ? 6 : 3>;
+    static_assert(!FM || LD::ENT <= 160, "a form build above 160 LDS entries per lane loses the fourth wave of a CU");
+    __shared__ R smem_[LD::ENT * L];
     const int lane = threadIdx.x;
-    Lds<R, N, NC, MODI, L> ld;
-    ld.b = (typename Lds<R, N, NC, MODI, L>::lptr)(smem_ + (lane < L ? lane : 0));   // lanes >= L hold no instance
+    LD ld;
+    ld.b = (typename LD::lptr)(smem_ + (lane < L ? lane : 0));   // lanes >= L hold no instance
     uint32_t* const q = P.queue;
     const long long B = P.B;
     const int max_iter = P.max_iter;
@@ -630,6 +684,8 @@ __global__ __launch_bounds__(64, 1) void lane_kernel(KP P)
                     double g0 = P.goal[2 * b], g1 = P.goal[2 * b + 1];
                     in.legp = P.leg[b] > 0;
                     const int ncr = P.nc[b];
+                    int ner = 0;
+                    if constexpr (FM) ner = P.ne ? P.ne[b] : 0;
                     in.act = 0;
                     // select_obs (MPC_LIP_modi.py:325-338) and the detour goal (MPC_LIP_modi.py:247-271): the
                     // first selected circle, in input order, that triggers
@@ -664,10 +720,42 @@ __global__ __launch_bounds__(64, 1) void lane_kernel(KP P)
                                 }
                             }
                         }
+                        double fqa = 0.0, fqb = 0.0, fqc = 0.0, fk = 0.0;
+                        if constexpr (FM) {
+                            // every entry of the slot is written for every instance: a circle is the form qa = qc = 1,
+                            // qb = 0, k = r^2; an unused slot is all zeros.  An ellipse [cx, cy, a, b, phi] in slot
+                            // nc_max + e: np_oracle.select_obs's range test on max(a, b), the coefficients in fp64
+                            // (oracle/np_oracle.py:198-203); it never fires the detour.
+                            const bool cs = j < ncr && j < P.nc_max;
+                            fqa = fqc = cs ? 1.0 : 0.0;
+                            fk = orr * orr;
+                            const int e = j - P.nc_max;
+                            if (e >= 0 && e < ner && e < P.ne_max) {
+                                const double* c = P.elp + ((size_t)b * P.ne_max + e) * 5;
+                                ox = c[0]; oy = c[1];
+                                const double ea = c[2], eb = c[3];
+                                const double rm = ea > eb ? ea : eb;
+                                const double cen = fma(x0d[0] - ox, x0d[0] - ox, (x0d[1] - oy) * (x0d[1] - oy));
+                                keep = !P.select_obs || cen - rm * rm <= P.detect_r2;
+                                double se, ce;
+                                lsincos_sel(c[4], &se, &ce);
+                                fqa = (eb * ce) * (eb * ce) + (ea * se) * (ea * se);
+                                fqb = 2 * ce * se * (eb * eb - ea * ea);
+                                fqc = (eb * se) * (eb * se) + (ea * ce) * (ea * ce);
+                                fk = (eb * ea) * (eb * ea);
+                            }
+                        }
                         in.act |= keep ? 1 << j : 0;
                         ld.ox(j) = (R)ox;   // (goal frame: shifted below, once the goal is known)
                         ld.oy(j) = (R)oy;
-                        ld.orr(j) = (R)(orr * orr);
+                        if constexpr (FM) {
+                            ld.orr(j) = (R)fk;
+                            ld.qa(j) = (R)fqa;
+                            ld.qb(j) = (R)fqb;
+                            ld.qc(j) = (R)fqc;
+                        } else {
+                            ld.orr(j) = (R)(orr * orr);
+                        }
                     }
                     if constexpr (GF) {
                         orgx = nx;
@@ -678,6 +766,14 @@ __global__ __launch_bounds__(64, 1) void lane_kernel(KP P)
                                 const double* c = P.cir + ((size_t)b * P.nc_max + j) * 3;
                                 ld.ox(j) = (R)(c[0] - nx);
                                 ld.oy(j) = (R)(c[1] - ny);
+                            }
+                            if constexpr (FM) {
+                                const int e = j - P.nc_max;
+                                if (e >= 0 && e < ner && e < P.ne_max) {
+                                    const double* c = P.elp + ((size_t)b * P.ne_max + e) * 5;
+                                    ld.ox(j) = (R)(c[0] - nx);
+                                    ld.oy(j) = (R)(c[1] - ny);
+                                }
                             }
                         }
                     }
@@ -818,16 +914,16 @@ __global__ __launch_bounds__(64, 1) void lane_kernel(KP P)
 #pragma unroll
                 for (int t = 0; t < 8; ++t) hp[t] = R(0);
                 R h0x = R(0);
+                R hxy = R(0), h0y = R(0), h0xy = R(0);   // (form build: the forms' cross terms and the y part on x_k)
                 R prod = R(1);
-                step_rows<NC, MODI>([&](auto KD_, int l, int j) {
+                step_rows<NC, MODI, FM>([&](auto KD_, int l, int j) {
                     constexpr int KD = decltype(KD_)::value;
                     const int i = k * RPS + l;
                     R cf[4], cl, cu, clo, cuo;
-                    const R c = row_eval<KD, R>(C, st, KD == CIR ? ld.ox(j) : R(0), KD == CIR ? ld.oy(j) : R(0),
-                                                KD == CIR ? ld.orr(j) : R(0), cf);
+                    const R c = row_value<KD, R>(C, st, ld, j, cf);
                     row_bounds<KD, R>(C, in.legp, k, cl, cu);
                     row_bounds<KD, R>(C, in.legp, k, clo, cuo, true);
-                    const bool act = KD != CIR || ((in.act >> j) & 1);
+                    const bool act = !is_obs<KD>() || ((in.act >> j) & 1);
                     const int zli_ = zl_index<N, NC, MODI>(k, l), zui_ = zu_index<N, NC, MODI>(k, l);
                     R si = ld.s(i);
                     R zli = has_lo<KD>() ? ld.zl(zli_) : R(0);
@@ -902,10 +998,10 @@ __global__ __launch_bounds__(64, 1) void lane_kernel(KP P)
                     RK jr[n];
 #pragma unroll
                     for (int t = 0; t < n; ++t) jr[t] = RK(0);
-                    constexpr int AX = (KD == CIR || KD == LEG) ? 3 : KD == DTH ? 4 : 7;
+                    constexpr int AX = (is_obs<KD>() || KD == LEG) ? 3 : KD == DTH ? 4 : 7;
 #pragma unroll
                     for (int t = 0; t < N; ++t) {
-                        if constexpr (KD == CIR) {
+                        if constexpr (is_obs<KD>()) {
                             jr[3 * t] = fma((RK)cf[0], z.sp1[t], (RK)cf[2] * z.sp0[t]);
                             jr[3 * t + 1] = fma((RK)cf[1], z.sp1[t], (RK)cf[3] * z.sp0[t]);
                         } else if constexpr (KD == LEG) {
@@ -941,6 +1037,15 @@ __global__ __launch_bounds__(64, 1) void lane_kernel(KP P)
                         hp[0] = fma(R(-2), y, hp[0]);
                         hp[2] = fma(R(-2), y, hp[2]);
                         h0x = fma(R(-2) * C[LK_GM1], y, h0x);
+                    } else if constexpr (KD == FRM) {
+                        // -y [[2 qa, qb], [qb, 2 qc]] on the position block of x_{k+1}, (gamma - 1) times it on x_k
+                        const R qa_ = ld.qa(j), qb_ = ld.qb(j), qc_ = ld.qc(j), gy = C[LK_GM1] * y;
+                        hp[0] = fma(R(-2) * qa_, y, hp[0]);
+                        hp[2] = fma(R(-2) * qc_, y, hp[2]);
+                        hxy = fma(-qb_, y, hxy);
+                        h0x = fma(R(-2) * qa_, gy, h0x);
+                        h0y = fma(R(-2) * qc_, gy, h0y);
+                        h0xy = fma(-qb_, gy, h0xy);
                     } else if constexpr (KD == LEG) {
                         // -y d2/dp2 |pos_k - f_k|^2 = -2 y u u^T per axis, u = d(px_k - fx_k)/dp
 #pragma unroll
@@ -981,7 +1086,7 @@ __global__ __launch_bounds__(64, 1) void lane_kernel(KP P)
                     }
                     RK h[6];
                     obj_parts<R>(C, in, k + 1, px, py, ph, og, h, dfo, orgx, orgy);
-                    hv[0] = (RK)hp[0] + h[0]; hv[1] = h[1]; hv[2] = (RK)hp[2] + h[2]; hv[3] = h[3]; hv[4] = h[4];
+                    hv[0] = (RK)hp[0] + h[0]; hv[1] = FM ? h[1] + (RK)hxy : h[1]; hv[2] = (RK)hp[2] + h[2]; hv[3] = h[3]; hv[4] = h[4];
                     hv[5] = (RK)hp[5]; hv[6] = (RK)hp[6]; hv[7] = (RK)hp[7] + h[5];
                 }
 #pragma unroll
@@ -1000,10 +1105,13 @@ __global__ __launch_bounds__(64, 1) void lane_kernel(KP P)
                         const RK pb = z.sp1[jb], tb = z.t1[jb], qb = z.sp0[jb];
                         if (jb <= ja) {
                             K[3 * ja][3 * jb] += fma(hv[0] * pa, pb, (RK)h0x * qa * qb);
-                            K[3 * ja + 1][3 * jb + 1] += fma(hv[2] * pa, pb, (RK)h0x * qa * qb);
+                            K[3 * ja + 1][3 * jb + 1] += fma(hv[2] * pa, pb, (RK)(FM ? h0y : h0x) * qa * qb);
                             K[3 * ja + 2][3 * jb + 2] += hv[7] * ta * tb;
                         }
-                        ksym<n, RK>(K, 3 * ja + 1, 3 * jb, hv[1] * pa * pb);   // (y_ja, x_jb)
+                        if constexpr (FM)
+                            ksym<n, RK>(K, 3 * ja + 1, 3 * jb, fma(hv[1] * pa, pb, (RK)h0xy * qa * qb));
+                        else
+                            ksym<n, RK>(K, 3 * ja + 1, 3 * jb, hv[1] * pa * pb);   // (y_ja, x_jb)
                         ksym<n, RK>(K, 3 * ja, 3 * jb + 2, hxt * tb);          // (x_ja, theta_jb)
                         ksym<n, RK>(K, 3 * ja + 1, 3 * jb + 2, hyt * tb);      // (y_ja, theta_jb)
                     }
@@ -1205,16 +1313,15 @@ __global__ __launch_bounds__(64, 1) void lane_kernel(KP P)
                         for (int k = 0; k < N; ++k) {
                             const Step<R> st = step_of<N, R>(pt.X, pt.cs, pt.sn, pr, k);
                             const Step<R> dst = step_of<N, R>(dX, pt.cs, pt.sn, dU, k);
-                            step_rows<NC, MODI>([&](auto KD_, int l, int j) {
+                            step_rows<NC, MODI, FM>([&](auto KD_, int l, int j) {
                                 constexpr int KD = decltype(KD_)::value;
                                 const int i = k * RPS + l;
                                 R cf[4], cl, cu;
-                                const R c = row_eval<KD, R>(C, st, KD == CIR ? ld.ox(j) : R(0), KD == CIR ? ld.oy(j) : R(0),
-                                                            KD == CIR ? ld.orr(j) : R(0), cf);
+                                const R c = row_value<KD, R>(C, st, ld, j, cf);
                                 row_bounds<KD, R>(C, in.legp, k, cl, cu);
-                                const bool act = KD != CIR || ((in.act >> j) & 1);
+                                const bool act = !is_obs<KD>() || ((in.act >> j) & 1);
                                 R jd;
-                                if constexpr (KD == CIR)
+                                if constexpr (is_obs<KD>())
                                     jd = cf[0] * dst.x1[0] + cf[1] * dst.x1[1] + cf[2] * dst.x0[0] + cf[3] * dst.x0[1];
                                 else if constexpr (KD == LEG)
                                     jd = cf[0] * dst.x0[0] + cf[1] * dst.x0[1] + cf[2] * dst.fx + cf[3] * dst.fy;
@@ -1338,14 +1445,13 @@ __global__ __launch_bounds__(64, 1) void lane_kernel(KP P)
                 for (int k = 0; k < N; ++k) {
                     const Step<R> st = step_of<N, R>(pt.X, pt.cs, pt.sn, ptr_, k);
                     R prod = R(1);
-                    step_rows<NC, MODI>([&](auto KD_, int l, int j) {
+                    step_rows<NC, MODI, FM>([&](auto KD_, int l, int j) {
                         constexpr int KD = decltype(KD_)::value;
                         const int i = k * RPS + l;
                         R cf[4], cl, cu;
-                        const R c = row_eval<KD, R>(C, st, KD == CIR ? ld.ox(j) : R(0), KD == CIR ? ld.oy(j) : R(0),
-                                                    KD == CIR ? ld.orr(j) : R(0), cf);
+                        const R c = row_value<KD, R>(C, st, ld, j, cf);
                         row_bounds<KD, R>(C, in.legp, k, cl, cu);
-                        const bool act = KD != CIR || ((in.act >> j) & 1);
+                        const bool act = !is_obs<KD>() || ((in.act >> j) & 1);
                         const R sv = fma(a, ld.ds(i), ld.s(i));
                         tht += act ? fabs(c - sv) : R(0);
                         R t = R(1);

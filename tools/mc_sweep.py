@@ -10,7 +10,10 @@ time of scenes.make_batch_vec for one 16,384-instance chunk.
 
   timeout 600 python tools/mc_sweep.py                      # cfg5's shape
   timeout 600 python tools/mc_sweep.py --scenes 65536 --n-cir 5 --n-elp 5 --horizon 5 --fields 4096   # dense mix
-With --n-elp > 0 the solve is the fp64 wave program (the lane program takes circles only).
+  timeout 600 python tools/mc_sweep.py --n-cir 3 --n-elp 2                                        # mix on the lane program
+The solve is the fp32 lane program where it serves the shape — horizon 3 with circles only (<= 6), or circles and
+ellipses with --n-cir + --n-elp <= 5 (its obstacle-form build: 2.5x the fp64 wave program's rate on 3 + 2 mix scenes,
+profiles/lane_elp/bench.jsonl) — and the fp64 wave program otherwise.
 --audit adds the plan audit (alipmpc_audit_batch) of every chunk's solutions on the same device buffers: one summary
 buffer is carried through all chunks and read once at the end; the JSON line gains "audit" (constraint violation x
 dense-trace clearance counts, the clearance histogram over --edges, the table by status class) and "audit_ms".
@@ -56,7 +59,7 @@ def main():
     count = a.scenes - a.first if a.count is None else a.count
     if a.first < 0 or count <= 0 or a.first + count > a.scenes:
         ap.error("--first / --count must select a non-empty range within --scenes")
-    lane = a.n_elp == 0 and a.horizon == 3
+    lane = a.horizon == 3 and (a.n_cir <= 6 if a.n_elp == 0 else a.n_cir + a.n_elp <= 5)
     kw = dict(precision=alipmpc.PREC_FP32, program=alipmpc.PROGRAM_LANE) if lane else {}
     cfg = alipmpc.default_cfg(alipmpc.VARIANT_MODI, a.horizon, nc_max=a.n_cir, ne_max=a.n_elp, **kw)
     torch.cuda.set_device(a.device)
