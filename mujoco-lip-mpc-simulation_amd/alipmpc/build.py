@@ -2,10 +2,12 @@
 
 The library is the product: there is no CPU execution path behind it.
 
-csrc/alipmpc.hip is compiled as 9 translation units in parallel — ALIP_PART=0 (host code, C ABI, rollout
-kernels, the scene generator of csrc/scenes.inc, the dataset rows of csrc/dataset.inc, the plan audit of csrc/audit.inc), ALIP_PART=1..6 (the solve/eval kernels of one horizon N each, fp64 and fp32) and ALIP_PART=7/8 (the
-lane solver of csrc/lane_solve.inc, fp64 / fp32) — and linked into one shared library.  `ALIPMPC_SINGLE_TU=1` builds it as one TU instead (slower, same code).
+csrc/alipmpc.hip, with every csrc/*.inc it includes (INCS), is compiled as 9 translation units in parallel —
+ALIP_PART=0 (host code and C ABI, rollout kernels, scene generator, dataset rows, plan audit), ALIP_PART=1..6 (the
+solve/eval kernels of one horizon N each, fp64 and fp32) and ALIP_PART=7/8 (the lane solver, fp64 / fp32) — and linked
+into one shared library.  `ALIPMPC_SINGLE_TU=1` builds it as one TU instead (slower, same code).
 """
+import glob
 import hashlib
 import os
 import subprocess
@@ -17,12 +19,9 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)                         # mujoco-lip-mpc-simulation_amd/
 REPO = os.path.dirname(ROOT)
 SRC = os.path.join(ROOT, "csrc", "alipmpc.hip")
-INC = os.path.join(ROOT, "csrc", "lane_solve.inc")
-MATH = os.path.join(ROOT, "csrc", "fastmath.inc")
-RESTO = os.path.join(ROOT, "csrc", "resto_wave.inc")
-SCN = os.path.join(ROOT, "csrc", "scenes.inc")
-DSET = os.path.join(ROOT, "csrc", "dataset.inc")
-AUD = os.path.join(ROOT, "csrc", "audit.inc")
+# every csrc/*.inc, taken as the files alipmpc.hip includes: a new include is never left out of the build id (and
+# nothing else belongs in csrc/ under that suffix)
+INCS = sorted(glob.glob(os.path.join(ROOT, "csrc", "*.inc")))
 HDR = os.path.join(REPO, "include", "alipmpc.h")
 LIB = os.path.join(PKG, "libalipmpc.so")
 PARTS = range(0, 9)
@@ -41,7 +40,7 @@ def build_id(extra=(), src=None):
     and the extra flags.  Compiled into the library (alipmpc_build_id) so a counter record made with one build is
     never attached to a bench line of another (tools/roofline.py, bench.py)."""
     h = hashlib.sha256()
-    for p in (src or SRC, INC, MATH, RESTO, SCN, DSET, AUD, HDR):
+    for p in (src or SRC, *INCS, HDR):
         with open(p, "rb") as fh:
             h.update(fh.read())
     h.update(" ".join([*ARCH, *FLAGS, *extra]).encode())
@@ -52,7 +51,7 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    return any(os.path.getmtime(p) > t for p in (SRC, INC, MATH, RESTO, SCN, DSET, AUD, HDR, __file__))
+    return any(os.path.getmtime(p) > t for p in (SRC, *INCS, HDR, __file__))
 
 
 def _run(cmd, verbose):

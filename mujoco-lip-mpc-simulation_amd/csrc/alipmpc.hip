@@ -1,6 +1,10 @@
 // alipmpc.hip — MI355X (gfx950) batched ALIP-MPC-CBF footstep planner: HIP kernels + the C ABI of
 // include/alipmpc.h.
 //
+// Files: this one holds the kernels, their parameter structs and launchers.  It includes fastmath.inc, resto_wave.inc
+// and lane_solve.inc (device code) and, into the host translation unit only, scenes.inc, dataset.inc, audit.inc (a kernel
+// each) and host_api.inc (all host code: constants, handle, argument staging, the extern "C" entry points).
+//
 // What it replaces (reference /root/reference):
 //   MPCCBF.select_obs / solveMPCCBF / gen_control_test rollout   MPC_LIP_modi.py:90-112, 197-301, 325-338
 //   LIP_Prob.objective / gradient / constraints / jacobian       MPC_LIP_modi.py:430-583 (+ helpers 586-655)
@@ -5461,1919 +5465,5 @@ __global__ __launch_bounds__(WAVE) void wave_helpers_kernel(const double* in, in
 #include "scenes.inc"   // counter-based scene generator (alipmpc_scenes_batch)
 #include "dataset.inc"  // row scan / compaction of alipmpc_closed_loop_dataset_batch
 #include "audit.inc"    // plan audit (alipmpc_audit_batch)
-
-// ================================================================================================
-// host side: constants, handle, C ABI
-// ================================================================================================
-namespace {
-
-using namespace alip;
-
-struct Handle {
-    alipmpc_cfg cfg;
-    int device = 0;
-    int N = 3, n = 9, NG = 32, NCP = 16, NCPU = 16, rps = 0, m_max = 0, mr4 = 0;
-    int rps_s = 0, m_s = 0, mr4_s = 0, mo4 = 0;   // solve-kernel row layout (f_en split, objective rows)
-    double* dGp = nullptr;
-    double* dEp = nullptr;
-    double* dGu = nullptr;
-    double* dEu = nullptr;
-    double* dau = nullptr;   // plan audit (audit.inc): trace matrices and the per-sample cosh / sinh table
-    // lane solver (lane_solve.inc): constants and the compiled circle-slot count it runs with (-1: the
-    // per-wave solve_kernel serves this configuration)
-    double* dlk = nullptr;
-    float* dlkf = nullptr;
-    int lane_nct = -1;
-    // eval hook: the circle-slot count sweep_kernel runs with (-1: eval_kernel serves this configuration)
-    int sweep_nc = -1;
-    // work-queue counter pairs of persistent solve launches (a ring: launches in flight on different
-    // streams use different pairs; each pair is reset by the last wave of the launch that used it), followed by
-    // MAXG pairs owned by the closed loop's episode groups (one per group)
-    static constexpr unsigned NQ = 64;
-    uint32_t* dq = nullptr;
-    mutable std::atomic<unsigned> qi{0};
-    // staging for host-pointer calls
-    void* stage = nullptr;
-    size_t stage_bytes = 0;
-    // rollout working set (evolving state, warm starts, per-step solve outputs)
-    void* rstage = nullptr;
-    size_t rstage_bytes = 0;
-    hipStream_t own = nullptr;
-    // closed loop: episode groups on streams of their own (ALIPMPC_CL_GROUPS), fork / join events
-    static constexpr int MAXG = 8;
-    hipStream_t gst[MAXG] = {};
-    hipEvent_t gev[MAXG + 1] = {};
-    // split launch of the wave program (ALIPMPC_SPLIT_IT): the phase-1 iteration cap (0 = off) and, per stream, the
-    // record buffer (launches on one stream run in order, so they may share it; other streams get their own)
-    int split_it = 0;
-    int split_tr = 0;   // phase-1 trial cut: an instance at this many line-search trials resumes as a team (0 = off)
-    int cl_split_it = 0, cl_split_tr = 0;   // the closed loop's per-tick solves (ALIPMPC_CL_SPLIT_IT / _TR)
-    // the paired phase 2 of the batch API's split (ALIPMPC_SPLIT_PAIR=0 turns it off): fp64 wave program with
-    // cfg.restoration = IPOPT, one row group per lane, 8 workspaces within the LDS; only without team records
-    bool split_pair = false;
-    // Record buffers are sized ONCE for the resident slots (the largest batch that splits) and never reallocated or
-    // freed before alipmpc_destroy, so a graph captured on a stream keeps a valid pointer whatever batch sizes run on
-    // that stream later.  At most SPLIT_STREAMS of them: a further stream runs the one-phase form.
-    static constexpr size_t SPLIT_STREAMS = 8;
-    struct SplitBuf {
-        void* p = nullptr;
-        size_t bytes = 0;
-    };
-    std::map<hipStream_t, SplitBuf> split;
-    std::mutex split_mtx;
-    // lane program with cfg.restoration = IPOPT: per stream, the list of instances handed to the wave program (count +
-    // indices; grown to the largest batch seen, never freed before alipmpc_destroy)
-    std::map<hipStream_t, SplitBuf> redo;
-    // launch timing: a ring of event pairs, so a re-record never targets an event still pending on the
-    // stream (that serialises the host with the previous launch)
-    static constexpr int NEV = 16;
-    hipEvent_t ev[NEV][2] = {};
-    int evi = 0, evlast = -1;
-    bool timed = false;
-    std::string err;
-};
-
-int fail(Handle* h, int code, const std::string& msg)
-{
-    if (h) h->err = msg;
-    return code;
-}
-
-#define HIPCHK(h, x)                                                                            \
-    do {                                                                                         \
-        hipError_t e_ = (x);                                                                     \
-        if (e_ != hipSuccess) return fail(h, ALIPMPC_EHIP, std::string(#x ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-void mm(const double* a, const double* b, double* c, int n1, int n2, int n3)
-{
-    for (int i = 0; i < n1; ++i)
-        for (int j = 0; j < n3; ++j) {
-            double s = 0;
-            for (int k = 0; k < n2; ++k) s += a[i * n2 + k] * b[k * n3 + j];
-            c[i * n3 + j] = s;
-        }
-}
-
-// generator tables.  Row 8k+c (c<5): state x_k[c]; row 8k+5+c (c<3): foothold p_k[c]; V = E x0 + G z.
-//  u-parametrisation (the reference's decision, eval + warm start): x_{k+1} = M_A x_k + M_B u_k,
-//    p_k = W(u_k - A x_k)                                           (MPC_LIP_modi.py:64-87, 630-634)
-//  foothold parametrisation (the solve): x_{k+1} = A x_k + B p_k   (W B = I, so the two describe the same
-//    NLP; u enters it only through W u_k, which leaves a 2N-dim null space in u that p removes)
-void build_tables(const alipmpc_cfg& cfg, int NCPP, int NCPU, std::vector<double>& Gp, std::vector<double>& Ep,
-                  std::vector<double>& Gu, std::vector<double>& Eu)
-{
-    const int N = cfg.N, n = 5 * N, np_ = 3 * N, NG = 8 * (N + 1);
-    const double b = std::sqrt(cfg.g / cfg.H), T = cfg.dt;
-    const double ch = std::cosh(b * T), sh = std::sinh(b * T);
-    double A[25] = {ch, 0, sh / b, 0, 0, 0, ch, 0, sh / b, 0, sh * b, 0, ch, 0, 0, 0, sh * b, 0, ch, 0, 0, 0, 0, 0, 1};
-    double Bm[15] = {1 - ch, 0, 0, 0, 1 - ch, 0, -sh * b, 0, 0, 0, -sh * b, 0, 0, 0, 1};
-    const double a_ = 5.0, b_ = 1.0;
-    const double Dd = a_ * (ch - 1) * (ch - 1) + b_ * (sh * b) * (sh * b);
-    const double Ch = -a_ * (ch - 1) / Dd, Sh = -b_ * sh * b / Dd;
-    double W[15] = {Ch, 0, Sh, 0, 0, 0, Ch, 0, Sh, 0, 0, 0, 0, 0, 1};
-    double MB[25], BWA[25], MA[25], WA[15];
-    mm(Bm, W, MB, 5, 3, 5);
-    mm(MB, A, BWA, 5, 5, 5);
-    for (int i = 0; i < 25; ++i) MA[i] = A[i] - BWA[i];
-    mm(W, A, WA, 3, 5, 5);
-    // ---- u tables
-    std::vector<double> Phi((N + 1) * 5 * n, 0.0), Pk((N + 1) * 25, 0.0);
-    for (int i = 0; i < 5; ++i) Pk[i * 5 + i] = 1.0;
-    for (int k = 1; k <= N; ++k) {
-        mm(MA, &Phi[(k - 1) * 5 * n], &Phi[k * 5 * n], 5, 5, n);
-        for (int i = 0; i < 5; ++i)
-            for (int j = 0; j < 5; ++j) Phi[k * 5 * n + i * n + 5 * (k - 1) + j] += MB[i * 5 + j];
-        mm(MA, &Pk[(k - 1) * 25], &Pk[k * 25], 5, 5, 5);
-    }
-    Gu.assign((size_t)NG * NCPU, 0.0);
-    Eu.assign((size_t)NG * 5, 0.0);
-    for (int k = 0; k <= N; ++k) {
-        for (int c = 0; c < 5; ++c) {
-            for (int j = 0; j < n; ++j) Gu[(8 * k + c) * NCPU + j] = Phi[k * 5 * n + c * n + j];
-            for (int j = 0; j < 5; ++j) Eu[(8 * k + c) * 5 + j] = Pk[k * 25 + c * 5 + j];
-        }
-        if (k < N) {
-            std::vector<double> WAPhi(3 * n), WAPk(15);
-            mm(WA, &Phi[k * 5 * n], WAPhi.data(), 3, 5, n);
-            mm(WA, &Pk[k * 25], WAPk.data(), 3, 5, 5);
-            for (int c = 0; c < 3; ++c) {
-                for (int j = 0; j < n; ++j) Gu[(8 * k + 5 + c) * NCPU + j] = -WAPhi[c * n + j];
-                for (int j = 0; j < 5; ++j) Gu[(8 * k + 5 + c) * NCPU + 5 * k + j] += W[c * 5 + j];
-                for (int j = 0; j < 5; ++j) Eu[(8 * k + 5 + c) * 5 + j] = -WAPk[c * 5 + j];
-            }
-        }
-    }
-    // ---- foothold tables: x_k = A^k x0 + sum_{j<k} A^{k-1-j} B p_j
-    std::vector<double> Ak((N + 1) * 25, 0.0);
-    for (int i = 0; i < 5; ++i) Ak[i * 5 + i] = 1.0;
-    for (int k = 1; k <= N; ++k) mm(A, &Ak[(k - 1) * 25], &Ak[k * 25], 5, 5, 5);
-    Gp.assign((size_t)NG * NCPP, 0.0);
-    Ep.assign((size_t)NG * 5, 0.0);
-    for (int k = 0; k <= N; ++k) {
-        for (int c = 0; c < 5; ++c) {
-            for (int j = 0; j < 5; ++j) Ep[(8 * k + c) * 5 + j] = Ak[k * 25 + c * 5 + j];
-            for (int jj = 0; jj < k; ++jj) {
-                double AB[15];
-                mm(&Ak[(k - 1 - jj) * 25], Bm, AB, 5, 5, 3);
-                for (int c2 = 0; c2 < 3; ++c2) Gp[(8 * k + c) * NCPP + 3 * jj + c2] = AB[c * 3 + c2];
-            }
-        }
-        if (k < N)
-            for (int c = 0; c < 3; ++c) Gp[(8 * k + 5 + c) * NCPP + 3 * k + c] = 1.0;
-    }
-    (void)np_;
-}
-
-// plan audit table (audit.inc, AU_TAB_*): the matrices alipmpc_trace_batch passes to trace_kernel and, per trace sample
-// t_i = i * 0.01, cosh(beta t_i), sinh(beta t_i) / beta, 1 - cosh(beta t_i)
-void audit_table(const alipmpc_cfg& cfg, std::vector<double>& tab)
-{
-    const int rows = alipmpc_trace_len(&cfg);
-    tab.assign((size_t)au_tab_doubles(rows), 0.0);
-    const double b = std::sqrt(cfg.g / cfg.H), dT = cfg.dt, ch = std::cosh(b * dT), sh = std::sinh(b * dT);
-    const double A[25] = {ch, 0, sh / b, 0, 0, 0, ch, 0, sh / b, 0, sh * b, 0, ch, 0, 0,
-                          0, sh * b, 0, ch, 0, 0, 0, 0, 0, 1};
-    const double Bm[15] = {1 - ch, 0, 0, 0, 1 - ch, 0, -sh * b, 0, 0, 0, -sh * b, 0, 0, 0, 1};
-    const double Dd = 5.0 * (ch - 1) * (ch - 1) + (sh * b) * (sh * b);
-    const double Ch = -5.0 * (ch - 1) / Dd, Sh = -sh * b / Dd;
-    const double W[15] = {Ch, 0, Sh, 0, 0, 0, Ch, 0, Sh, 0, 0, 0, 0, 0, 1};
-    double BWA[25];
-    std::memcpy(&tab[AU_TAB_A], A, sizeof(A));
-    std::memcpy(&tab[AU_TAB_W], W, sizeof(W));
-    mm(Bm, W, &tab[AU_TAB_MB], 5, 3, 5);
-    mm(&tab[AU_TAB_MB], A, BWA, 5, 5, 5);
-    for (int i = 0; i < 25; ++i) tab[AU_TAB_MA + i] = A[i] - BWA[i];
-    for (int i = 0; i + 1 < rows; ++i) {
-        const double t = i * 0.01, c = std::cosh(b * t), s = std::sinh(b * t);
-        tab[AU_TAB_S + 3 * i] = c;
-        tab[AU_TAB_S + 3 * i + 1] = s / b;
-        tab[AU_TAB_S + 3 * i + 2] = 1 - c;
-    }
-}
-
-// lane-solver constants (lane::LK_* slots): the ALIP step map per axis, W, the foothold sensitivities
-// d px_k / d fx_j = (Abar^(k-1-j) bbar)[0] and d vx_k / d fx_j = (...)[1], the relaxed (IPOPT
-// bound_relax_factor 1e-8, as the oracle) and original bounds, weights and tolerances
-void lane_constants(const alipmpc_cfg& cfg, double* lk)
-{
-    using namespace alip::lane;
-    static_assert(LK_COUNT <= LK_BUF, "lane constants fit their buffer");
-    for (int i = 0; i < LK_BUF; ++i) lk[i] = 0.0;
-    const double b = std::sqrt(cfg.g / cfg.H), T = cfg.dt;
-    const double ch = std::cosh(b * T), sh = std::sinh(b * T);
-    lk[LK_CH] = ch;
-    lk[LK_SHB] = sh / b;
-    lk[LK_BSH] = sh * b;
-    lk[LK_OMC] = 1.0 - ch;
-    const double a_ = 5.0, b_ = 1.0;
-    const double Dd = a_ * (ch - 1) * (ch - 1) + b_ * (sh * b) * (sh * b);
-    lk[LK_WCH] = -a_ * (ch - 1) / Dd;
-    lk[LK_WSH] = -b_ * sh * b / Dd;
-    double v0 = 1.0 - ch, v1 = -sh * b;
-    for (int m = 0; m < 6; ++m) {
-        lk[LK_SP + m] = v0;
-        lk[LK_SV + m] = v1;
-        const double w0 = ch * v0 + (sh / b) * v1, w1 = sh * b * v0 + ch * v1;
-        v0 = w0;
-        v1 = w1;
-    }
-    auto rl = [](double x) { return x - 1e-8 * std::fmax(1.0, std::fabs(x)); };
-    auto ru = [](double x) { return x + 1e-8 * std::fmax(1.0, std::fabs(x)); };
-    lk[LK_VXL] = rl(cfg.bvx_lo);
-    lk[LK_VXU] = ru(cfg.bvx_hi);
-    lk[LK_VYLP] = rl(cfg.bvy_lo);
-    lk[LK_VYUP] = ru(cfg.bvy_hi);
-    lk[LK_VYLN] = rl(-cfg.bvy_hi);
-    lk[LK_VYUN] = ru(-cfg.bvy_lo);
-    lk[LK_CIRL] = rl(0.0);
-    lk[LK_LEGL] = rl(0.0);
-    lk[LK_LEGU] = ru(cfg.leg2_max);
-    lk[LK_DTL] = rl(-cfg.dtheta_max);
-    lk[LK_DTU] = ru(cfg.dtheta_max);
-    lk[LK_OVXL] = cfg.bvx_lo;
-    lk[LK_OVXU] = cfg.bvx_hi;
-    lk[LK_OVYLP] = cfg.bvy_lo;
-    lk[LK_OVYUP] = cfg.bvy_hi;
-    lk[LK_OVYLN] = -cfg.bvy_hi;
-    lk[LK_OVYUN] = -cfg.bvy_lo;
-    lk[LK_OLEGU] = cfg.leg2_max;
-    lk[LK_ODT] = cfg.dtheta_max;
-    lk[LK_Q] = cfg.q;
-    lk[LK_P] = cfg.p;
-    lk[LK_R] = cfg.r;
-    lk[LK_GM1] = cfg.gamma - 1.0;
-    lk[LK_S] = cfg.s;
-    lk[LK_TOL] = cfg.tol;
-    lk[LK_ACC] = cfg.acceptable_tol;
-    lk[LK_MU0] = cfg.mu_init;
-    lk[LK_DET2] = cfg.detect_r2;
-    // d px_{k+1+m} / d u_k[px], [vx] of the reference's u (per axis: (MA^m MB)[0][0], [0][1], MA = (I - B W) A, MB = B W),
-    // for IPOPT's objective scaling at the starting point (lane_solve.inc)
-    {
-        const double Ax[2][2] = {{ch, sh / b}, {sh * b, ch}}, Bx[2] = {1.0 - ch, -sh * b};
-        const double Wx[2] = {lk[LK_WCH], lk[LK_WSH]};
-        double MA[2][2], MB[2][2], Mm[2][2] = {{1, 0}, {0, 1}};   // Mm = MA^m
-        for (int i = 0; i < 2; ++i)
-            for (int j = 0; j < 2; ++j) {
-                MB[i][j] = Bx[i] * Wx[j];
-                MA[i][j] = Ax[i][j] - Bx[i] * (Wx[0] * Ax[0][j] + Wx[1] * Ax[1][j]);
-            }
-        for (int m = 0; m < 6; ++m) {
-            lk[LK_SU0 + m] = Mm[0][0] * MB[0][0] + Mm[0][1] * MB[1][0];
-            lk[LK_SU1 + m] = Mm[0][0] * MB[0][1] + Mm[0][1] * MB[1][1];
-            double T[2][2];
-            for (int i = 0; i < 2; ++i)
-                for (int j = 0; j < 2; ++j) T[i][j] = Mm[i][0] * MA[0][j] + Mm[i][1] * MA[1][j];
-            for (int i = 0; i < 2; ++i)
-                for (int j = 0; j < 2; ++j) Mm[i][j] = T[i][j];
-        }
-    }
-}
-
-// the compiled lane-solver instance serving cfg, or -1 when none does: N = 3 with circles only (<= 6 circle slots),
-// modi / sig_step (BASELINE cfg1/2/4/5 shapes); with ellipses (ne_max >= 1) modi's form build, nc_max + ne_max <= 5
-// (LANE_FORM5: its 157 LDS entries per lane keep four waves on a CU, a sixth slot would not — lane_solve.inc)
-int lane_slots_for(const alipmpc_cfg& c)
-{
-    if (c.variant == ALIPMPC_VARIANT_DD || c.N != 3) return -1;
-    if (c.ne_max != 0)
-        return c.variant == ALIPMPC_VARIANT_MODI && c.ne_max >= 1 && c.nc_max + c.ne_max <= 5 ? LANE_FORM5 : -1;
-    if (c.nc_max > 6) return -1;
-    return c.nc_max == 0 ? 0 : c.nc_max <= 5 ? 5 : 6;
-}
-
-size_t smem_bytes(const Handle* h, bool solve, int force_f64 = 0)
-{
-    if (h->cfg.variant == ALIPMPC_VARIANT_DD) {
-        int wsd = 0;
-        switch (h->N) {
-#define DDCASE(NN) \
-    case NN: wsd = ddw_doubles<NN>(h->cfg.nc_max + h->cfg.ne_max, h->mo4); break;
-            DDCASE(1) DDCASE(2) DDCASE(3) DDCASE(4) DDCASE(5) DDCASE(6)
-#undef DDCASE
-        }
-        (void)solve;
-        return sizeof(double) * ((size_t)KP_DOUBLES + (size_t)WAVES_PER_BLOCK * wsd);
-    }
-    const bool f32 = solve && h->cfg.precision == ALIPMPC_PREC_FP32 && !force_f64;
-    int wsd = 0;
-    switch (h->N) {
-#define WSCASE(NN)                                                                                     \
-    case NN:                                                                                           \
-        wsd = solve ? (f32 ? wss_elems<NN, float>(h->cfg.nc_max, h->cfg.ne_max, h->mr4_s, h->mo4)      \
-                           : wss_elems<NN, double>(h->cfg.nc_max, h->cfg.ne_max, h->mr4_s, h->mo4)) \
-                    : gws_doubles<NN>(h->cfg.nc_max, h->cfg.ne_max, h->mr4);                           \
-        break;
-        WSCASE(1) WSCASE(2) WSCASE(3) WSCASE(4) WSCASE(5) WSCASE(6)
-#undef WSCASE
-    }
-    const int e = solve ? 0 : h->NG * 5 + ((h->NG * 5) & 1);   // (solve_kernel: E from global memory)
-    const int ncp = solve ? h->NCP : h->NCPU;
-    // KP in fp64 units, then G, E and the per-wave workspaces in the kernel's arithmetic type
-    const size_t per_block = solve ? (size_t)WAVES_PER_BLOCK : (size_t)GROUPS_PER_BLOCK;   // workspaces
-    return sizeof(double) * (size_t)KP_DOUBLES +
-           (f32 ? sizeof(float) : sizeof(double)) * ((size_t)h->NG * ncp + e + per_block * wsd);
-}
-
-KP make_kp(const Handle* h, long long B, bool solve)
-{
-    const alipmpc_cfg& c = h->cfg;
-    KP P;
-    std::memset(&P, 0, sizeof(P));
-    P.nc_max = c.nc_max;
-    P.ne_max = c.ne_max;
-    P.rps = solve ? h->rps_s : h->rps;
-    P.m_max = solve ? h->m_s : h->m_max;
-    P.mr4 = solve ? h->mr4_s : h->mr4;
-    P.mo4 = h->mo4;
-    P.modi = c.variant == ALIPMPC_VARIANT_MODI;
-    P.max_iter = c.max_iter;
-    P.select_obs = c.select_obs;
-    P.detour = c.detour;
-    P.goal_abort = c.goal_singular == ALIPMPC_GOAL_SINGULAR_ABORT;
-    P.resto_ipopt = c.restoration == ALIPMPC_RESTORATION_IPOPT && c.variant != ALIPMPC_VARIANT_DD;
-    P.tol = c.tol;
-    P.acc_tol = c.acceptable_tol;
-    P.q = c.q;
-    P.p = c.p;
-    P.r = c.r;
-    P.gm1 = c.gamma - 1.0;
-    P.s = c.s;
-    P.detect_r2 = c.detect_r2;
-    P.leg2 = c.leg2_max;
-    P.bvx_lo = c.bvx_lo;
-    P.bvx_hi = c.bvx_hi;
-    P.bvy_lo = c.bvy_lo;
-    P.bvy_hi = c.bvy_hi;
-    P.dth = c.dtheta_max;
-    P.mu_init = c.mu_init;
-    P.dt = c.dt;
-    P.dd_t = c.dd_t;
-    P.G = solve ? h->dGp : h->dGu;
-    P.E = solve ? h->dEp : h->dEu;
-    P.Gu = h->dGu;
-    P.Eu = h->dEu;
-    P.B = B;
-    P.lkd = h->dlk;
-    P.lkfd = h->dlkf;
-    if (solve && c.variant != ALIPMPC_VARIANT_DD) P.queue = h->dq + 2 * (h->qi.fetch_add(1u) % Handle::NQ);
-    return P;
-}
-
-// J-layout steps (4 rows each) of the compiled solve kernels; mo4 is rounded up to 4 * ksm_of(rows)
-int ksm_of(int rows)
-{
-    static const int K[] = {4, 8, 10, 12, 16, 24, 32, 48};
-    for (int k : K)
-        if (rows <= 4 * k) return k;
-    return 1 << 20;
-}
-
-// cfg.restoration = IPOPT, fp32 programs and the lane program: the stream's hand-off list ([0] = count, then the
-// instances), allocated outside a capture (a capture needs an uncaptured solve of that size on the stream first)
-static hipError_t redo_list(const Handle* h, hipStream_t st, long long B, uint32_t** out)
-{
-    Handle* hm = const_cast<Handle*>(h);
-    std::lock_guard<std::mutex> lk(hm->split_mtx);
-    Handle::SplitBuf& rb = hm->redo[st];
-    const size_t need = sizeof(uint32_t) * (size_t)(B + 1);
-    if (rb.bytes < need) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return hipErrorNotSupported;
-        if (rb.p) {
-            (void)hipStreamSynchronize(st);
-            (void)hipFree(rb.p);
-            rb.p = nullptr;
-            rb.bytes = 0;
-        }
-        if (hipError_t e = hipMalloc(&rb.p, need)) return e;
-        rb.bytes = need;
-    }
-    *out = (uint32_t*)rb.p;
-    return hipSuccess;
-}
-
-// the listed instances, solved from their start by the fp64 wave program's restoration-capable work queue (slot k
-// solves redo[1 + k], k < redo[0]) on the same stream
-static hipError_t launch_handoff(const Handle* h, const KP& P, const uint32_t* redo, hipStream_t st)
-{
-    KP Q = P;
-    Q.redo = nullptr;
-    Q.order = reinterpret_cast<const int32_t*>(redo + 1);
-    Q.bcount = redo;
-    Q.ckpt = nullptr;
-    Q.cont = nullptr;
-    Q.resume = 0;
-    Q.team = 0;
-    Q.ckpt_it = 0;
-    Q.ckpt_tr = 0;
-    const size_t sm = smem_bytes(h, true, 1);
-    switch (h->N) {
-    case 1: return launch_lip_1(true, false, Q, sm, st, nullptr);
-    case 2: return launch_lip_2(true, false, Q, sm, st, nullptr);
-    case 3: return launch_lip_3(true, false, Q, sm, st, nullptr);
-    case 4: return launch_lip_4(true, false, Q, sm, st, nullptr);
-    case 5: return launch_lip_5(true, false, Q, sm, st, nullptr);
-    case 6: return launch_lip_6(true, false, Q, sm, st, nullptr);
-    }
-    return hipErrorInvalidValue;
-}
-
-// res_out != null: no launch, report the resident workgroups of the solve kernel (0 for DD: no queue)
-hipError_t launch(const Handle* h, bool solve, const KP& P, hipStream_t st, unsigned* res_out = nullptr)
-{
-    const size_t smem = smem_bytes(h, solve);
-    const bool f32 = h->cfg.precision == ALIPMPC_PREC_FP32;
-    if (h->cfg.variant == ALIPMPC_VARIANT_DD && res_out) {
-        *res_out = 0;
-        return hipSuccess;
-    }
-    if (h->cfg.variant == ALIPMPC_VARIANT_DD) {
-        switch (h->N) {
-        case 1: return launch_dd_1(solve, P, smem, st);
-        case 2: return launch_dd_2(solve, P, smem, st);
-        case 3: return launch_dd_3(solve, P, smem, st);
-        case 4: return launch_dd_4(solve, P, smem, st);
-        case 5: return launch_dd_5(solve, P, smem, st);
-        case 6: return launch_dd_6(solve, P, smem, st);
-        }
-        return hipErrorInvalidValue;
-    }
-    if (!solve && h->sweep_nc >= 0) {
-        if (res_out) return hipErrorInvalidValue;
-        return launch_sweep(h->sweep_nc, h->cfg.variant == ALIPMPC_VARIANT_MODI, P, st);
-    }
-    if (solve && h->lane_nct >= 0) {
-        const bool modi = h->cfg.variant == ALIPMPC_VARIANT_MODI;
-        if (res_out || !P.resto_ipopt)
-            return f32 ? launch_lane_f32(h->lane_nct, modi, P, st, res_out) : launch_lane_f64(h->lane_nct, modi, P, st, res_out);
-        // cfg.restoration = IPOPT: the lane program solves every instance whose line searches all succeed; an instance
-        // whose search fails is listed (P.redo) and solved from its start by the fp64 wave program's restoration-capable
-        // work queue, on the same stream (the same queue pair: the lane kernel's last wave resets it)
-        KP P1 = P;
-        if (hipError_t e = redo_list(h, st, P.B, &P1.redo)) return e;
-        if (hipError_t e = hipMemsetAsync(P1.redo, 0, sizeof(uint32_t), st)) return e;
-        if (hipError_t e = f32 ? launch_lane_f32(h->lane_nct, modi, P1, st, nullptr)
-                               : launch_lane_f64(h->lane_nct, modi, P1, st, nullptr))
-            return e;
-        return launch_handoff(h, P, P1.redo, st);
-    }
-    if (solve && f32 && P.resto_ipopt && !res_out && !P.redo) {
-        // the fp32 wave program, cfg.restoration = IPOPT: the same hand-off (solve_one lists an instance whose search
-        // fails).  Phase 1 of a split launch starts the list and phase 2 continues it; the fp64 work queue runs after
-        // the last launch of the solve.
-        KP P1 = P;
-        if (hipError_t e = redo_list(h, st, P.B, &P1.redo)) return e;
-        if (!P.resume)
-            if (hipError_t e = hipMemsetAsync(P1.redo, 0, sizeof(uint32_t), st)) return e;
-        if (hipError_t e = launch(h, true, P1, st)) return e;
-        if (P.ckpt && !P.resume) return hipSuccess;
-        return launch_handoff(h, P, P1.redo, st);
-    }
-    switch (h->N) {
-    case 1: return launch_lip_1(solve, f32, P, smem, st, res_out);
-    case 2: return launch_lip_2(solve, f32, P, smem, st, res_out);
-    case 3: return launch_lip_3(solve, f32, P, smem, st, res_out);
-    case 4: return launch_lip_4(solve, f32, P, smem, st, res_out);
-    case 5: return launch_lip_5(solve, f32, P, smem, st, res_out);
-    case 6: return launch_lip_6(solve, f32, P, smem, st, res_out);
-    }
-    return hipErrorInvalidValue;
-}
-
-// hip_stream argument -> the stream to launch on (NULL = host-pointer mode on the handle's own stream,
-// ALIPMPC_STREAM_NULL = device pointers on the null stream)
-hipStream_t stream_of(const Handle* h, void* hip_stream)
-{
-    if (!hip_stream) return h->own;
-    if (hip_stream == ALIPMPC_STREAM_NULL) return nullptr;
-    return (hipStream_t)hip_stream;
-}
-
-bool create_events(Handle* h)
-{
-    for (auto& pr : h->ev)
-        for (hipEvent_t& e : pr)
-            if (hipEventCreate(&e) != hipSuccess) return false;
-    return true;
-}
-
-int ensure_stage(Handle* h, size_t bytes)
-{
-    if (h->stage_bytes >= bytes) return 0;
-    if (h->stage) hipFree(h->stage);
-    h->stage = nullptr;
-    h->stage_bytes = 0;
-    HIPCHK(h, hipMalloc(&h->stage, bytes));
-    h->stage_bytes = bytes;
-    return 0;
-}
-
-struct Carver {
-    char* base;
-    size_t off = 0;
-    template <class T>
-    T* take(size_t count)
-    {
-        off = (off + 255) & ~(size_t)255;
-        T* p = reinterpret_cast<T*>(base + off);
-        off += count * sizeof(T);
-        return p;
-    }
-};
-
-}  // namespace
-
-extern "C" {
-
-int alipmpc_default_cfg(int32_t variant, int32_t N, alipmpc_cfg* c)
-{
-    if (!c) return ALIPMPC_EINVAL;
-    std::memset(c, 0, sizeof(*c));
-    c->N = N;
-    c->nc_max = 6;
-    c->ne_max = 6;
-    c->variant = variant;
-    // the reference's IPOPT caps: MPC_LIP_modi.py:287 (30), MPC_LIP_sig_step.py:269 (20), MPC_DD_sig_step.py:183 (40)
-    c->max_iter = variant == ALIPMPC_VARIANT_SIG_STEP ? 20 : variant == ALIPMPC_VARIANT_DD ? 40 : 30;
-    c->precision = ALIPMPC_PREC_FP64;
-    c->select_obs = 1;
-    c->detour = 1;
-    c->tol = 1e-8;
-    c->acceptable_tol = 1e-6;
-    c->dt = 0.4;
-    c->H = 1.0;
-    c->g = 9.81;
-    c->leg2_max = 0.09;
-    c->bvx_lo = 0.4;
-    c->bvx_hi = 0.8;
-    c->bvy_lo = 0.15;
-    c->bvy_hi = 0.35;
-    c->dtheta_max = M_PI / 16;
-    c->q = 1.0;
-    c->p = 0.0;
-    c->r = 50.0;
-    c->gamma = 0.2;
-    c->s = 0.024 * 180 / M_PI;
-    c->detect_r2 = 16.0;
-    c->dd_t = 2.0;
-    c->mu_init = 0.1;
-    if (variant == ALIPMPC_VARIANT_SIG_STEP) {   // MPC_LIP_sig_step.py:38,340-353
-        c->bvy_hi = 0.30;
-        c->p = 2.0;
-        c->r = 15.0;
-        c->gamma = 0.4;
-        c->s = 0.014 * 180 / M_PI;
-        c->select_obs = 0;
-    } else if (variant == ALIPMPC_VARIANT_DD) {  // MPC_DD_sig_step.py:33-37,323-338
-        c->select_obs = 0;
-        c->detour = 0;
-    } else if (variant != ALIPMPC_VARIANT_MODI) {
-        return ALIPMPC_EINVAL;
-    }
-    return ALIPMPC_OK;
-}
-
-int32_t alipmpc_rows_per_step(const alipmpc_cfg* c)
-{
-    if (!c) return 0;
-    if (c->variant == ALIPMPC_VARIANT_DD) return c->nc_max + c->ne_max + 1;
-    return 4 + c->nc_max + c->ne_max + (c->variant == ALIPMPC_VARIANT_MODI ? 1 : 0);
-}
-
-int32_t alipmpc_num_vars(const alipmpc_cfg* c)
-{
-    if (!c) return 0;
-    return c->variant == ALIPMPC_VARIANT_DD ? 2 * c->N : 5 * c->N;
-}
-
-int alipmpc_create(const alipmpc_cfg* cfg, int device, void** handle)
-{
-    if (!cfg || !handle) return ALIPMPC_EINVAL;
-    *handle = nullptr;
-    if (cfg->N < 1 || cfg->N > ALIPMPC_MAX_N || cfg->nc_max < 0 || cfg->ne_max < 0 ||
-        cfg->nc_max + cfg->ne_max > ALIPMPC_MAX_OBS || cfg->max_iter < 0 || cfg->max_iter > FILTER_CAP - 2)
-        return ALIPMPC_EINVAL;
-    if (cfg->precision != ALIPMPC_PREC_FP64 && cfg->precision != ALIPMPC_PREC_FP32) return ALIPMPC_EINVAL;
-    if (cfg->program != ALIPMPC_PROGRAM_WAVE && cfg->program != ALIPMPC_PROGRAM_LANE) return ALIPMPC_EINVAL;
-    // enum fields: callers start from alipmpc_default_cfg (a struct filled by hand must set them to a defined value)
-    if (cfg->goal_singular != ALIPMPC_GOAL_SINGULAR_ZERO && cfg->goal_singular != ALIPMPC_GOAL_SINGULAR_ABORT)
-        return ALIPMPC_EINVAL;
-    if (cfg->restoration != ALIPMPC_RESTORATION_IPOPT && cfg->restoration != ALIPMPC_RESTORATION_SUBSTITUTE)
-        return ALIPMPC_EINVAL;
-    // fp32 arithmetic is implemented for the LIP solve kernels (modi, sig_step)
-    if (cfg->precision == ALIPMPC_PREC_FP32 && cfg->variant == ALIPMPC_VARIANT_DD) return ALIPMPC_EUNSUPPORTED;
-    if (cfg->variant != ALIPMPC_VARIANT_MODI && cfg->variant != ALIPMPC_VARIANT_SIG_STEP &&
-        cfg->variant != ALIPMPC_VARIANT_DD)
-        return ALIPMPC_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return ALIPMPC_ENODEV;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return ALIPMPC_ENODEV;
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return ALIPMPC_ENODEV;
-    Handle* h = new Handle();
-    h->cfg = *cfg;
-    if (cfg->precision == ALIPMPC_PREC_FP32 && cfg->tol == 1e-8 && cfg->acceptable_tol == 1e-6) {
-        // the fp64 defaults are below fp32 resolution: use the horizon-aware fp32 defaults (the ctypes
-        // layer's FP32_TOL*); N > 3 decision-space gradients grow through A^k and lift the fp32 floor
-        h->cfg.tol = cfg->N > 3 ? 3e-4 : 1e-4;
-        h->cfg.acceptable_tol = cfg->N > 3 ? 3e-3 : 1e-3;
-    }
-    h->device = device;
-    h->N = cfg->N;
-    h->n = 3 * cfg->N;
-    h->NG = 8 * (cfg->N + 1);
-    h->NCP = 16 * ((h->n + 15) / 16);
-    h->NCPU = 16 * ((5 * cfg->N + 15) / 16);
-    h->rps = alipmpc_rows_per_step(cfg);
-    h->m_max = cfg->N * h->rps;
-    h->mr4 = (h->m_max + 3) & ~3;
-    if (cfg->variant == ALIPMPC_VARIANT_DD) {
-        // DD solve rows per step: cbf slots, v +- s w, v bound, w bound; + N objective rows; whole
-        // 64-lane row groups (dd_solve_kernel<N, RPL>)
-        h->rps_s = cfg->nc_max + cfg->ne_max + 4;
-        h->m_s = cfg->N * h->rps_s;
-        h->mr4_s = (h->m_s + 3) & ~3;
-        const int rpl = (h->mr4_s + cfg->N + WAVE - 1) / WAVE;
-        h->mo4 = rpl <= 3 ? WAVE * rpl : 1 << 20;
-    } else {
-        h->rps_s = h->rps + (cfg->variant == ALIPMPC_VARIANT_MODI ? 1 : 0);   // f_en -> two smooth rows
-        h->m_s = cfg->N * h->rps_s;
-        h->mr4_s = (h->m_s + 3) & ~3;
-        // + the objective pseudo-rows of the solve kernel, rounded up to the compiled J-layout size (4 KSM)
-        h->mo4 = 4 * ksm_of(h->mr4_s + 4 * ((cfg->N + 3) / 4));
-    }
-    if (h->mr4 > MAX_ROWS || h->mo4 > MAX_ROWS + 64) {
-        delete h;
-        return ALIPMPC_EINVAL;
-    }
-    if (hipSetDevice(device) != hipSuccess) {
-        delete h;
-        return ALIPMPC_ENODEV;
-    }
-    std::vector<double> Gp, Ep, Gu, Eu;
-    build_tables(*cfg, h->NCP, h->NCPU, Gp, Ep, Gu, Eu);
-    auto up = [](double** d, const std::vector<double>& v) {
-        return hipMalloc(d, v.size() * sizeof(double)) == hipSuccess &&
-               hipMemcpy(*d, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-    };
-    if (!up(&h->dGp, Gp) || !up(&h->dEp, Ep) || !up(&h->dGu, Gu) || !up(&h->dEu, Eu) ||
-        hipMalloc(&h->dq, 2 * (Handle::NQ + Handle::MAXG) * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc(&h->dlk, alip::lane::LK_BUF * sizeof(double)) != hipSuccess ||
-        hipMalloc(&h->dlkf, alip::lane::LK_BUF * sizeof(float)) != hipSuccess ||
-        hipMemset(h->dq, 0, 2 * (Handle::NQ + Handle::MAXG) * sizeof(uint32_t)) != hipSuccess ||
-        hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking) != hipSuccess ||
-        !create_events(h)) {
-        alipmpc_destroy(h);
-        return ALIPMPC_EHIP;
-    }
-    if (cfg->variant != ALIPMPC_VARIANT_DD && alipmpc_trace_len(cfg) > 1) {
-        std::vector<double> au;
-        audit_table(h->cfg, au);
-        if (!up(&h->dau, au)) {
-            alipmpc_destroy(h);
-            return ALIPMPC_EHIP;
-        }
-    }
-    {
-        double lk[alip::lane::LK_BUF];
-        float lkf[alip::lane::LK_BUF];
-        lane_constants(h->cfg, lk);
-        for (int i = 0; i < alip::lane::LK_BUF; ++i) lkf[i] = (float)lk[i];
-        if (hipMemcpy(h->dlk, lk, sizeof(lk), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(h->dlkf, lkf, sizeof(lkf), hipMemcpyHostToDevice) != hipSuccess) {
-            alipmpc_destroy(h);
-            return ALIPMPC_EHIP;
-        }
-        // the eval hook's sweep kernel: N = 3, circle slots only (ALIPMPC_EVAL_KERNEL=group selects eval_kernel,
-        // for A/B and the bit-identity test)
-        const char* ek = std::getenv("ALIPMPC_EVAL_KERNEL");
-        if (h->cfg.variant != ALIPMPC_VARIANT_DD && h->cfg.N == 3 && h->cfg.ne_max == 0 && h->cfg.nc_max <= 6 &&
-            !(ek && std::strcmp(ek, "group") == 0))
-            h->sweep_nc = h->cfg.nc_max;
-        {   // split launch of one-wave-per-instance batches (ALIPMPC_SPLIT_IT=0 turns it off)
-            const char* se = std::getenv("ALIPMPC_SPLIT_IT");
-            h->split_it = se ? std::atoi(se)
-                             : (cfg->restoration == ALIPMPC_RESTORATION_IPOPT ? SPLIT_IT_DEFAULT_RESTO : SPLIT_IT_DEFAULT);
-            if (h->split_it < 0 || h->split_it >= h->cfg.max_iter) h->split_it = 0;
-            auto env_int = [](const char* name, int dflt) {
-                const char* t = std::getenv(name);
-                return t ? std::max(0, std::atoi(t)) : dflt;
-            };
-            h->split_tr = env_int("ALIPMPC_SPLIT_TR", SPLIT_TR_DEFAULT);
-            h->cl_split_it = env_int("ALIPMPC_CL_SPLIT_IT", CL_SPLIT_IT_DEFAULT);
-            if (h->cl_split_it >= h->cfg.max_iter) h->cl_split_it = 0;
-            h->cl_split_tr = env_int("ALIPMPC_CL_SPLIT_TR", CL_SPLIT_TR_DEFAULT);
-        }
-        if (h->cfg.program == ALIPMPC_PROGRAM_LANE) {
-            h->lane_nct = lane_slots_for(h->cfg);
-            if (h->lane_nct < 0) {
-                alipmpc_destroy(h);
-                return ALIPMPC_EUNSUPPORTED;
-            }
-        }
-    }
-    // (fp32 with cfg.restoration = IPOPT hands instances to the fp64 wave program: its workspace must fit as well)
-    const bool handoff = cfg->variant != ALIPMPC_VARIANT_DD && cfg->restoration == ALIPMPC_RESTORATION_IPOPT &&
-                         (cfg->precision == ALIPMPC_PREC_FP32 || h->lane_nct >= 0);
-    if (smem_bytes(h, true) > 160 * 1024 || smem_bytes(h, false) > 160 * 1024 ||
-        (handoff && smem_bytes(h, true, 1) > 160 * 1024)) {
-        alipmpc_destroy(h);
-        return ALIPMPC_EUNSUPPORTED;
-    }
-    // team records need the team-capable build's TEAM_WAVES workspaces in one workgroup: without room, no trial cut
-    if (cfg->variant != ALIPMPC_VARIANT_DD && cfg->precision != ALIPMPC_PREC_FP32 && h->lane_nct < 0) {
-        size_t st_ = 0;
-        switch (h->N) {
-#define TSCASE(NN) \
-    case NN: st_ = team_smem<NN, double>(smem_bytes(h, true)); break;
-            TSCASE(1) TSCASE(2) TSCASE(3) TSCASE(4) TSCASE(5) TSCASE(6)
-#undef TSCASE
-        }
-        if (st_ > 160 * 1024) h->split_tr = h->cl_split_tr = 0;
-        // the paired phase 2 (solve_kernel<..., PR>): where its 8 workspaces fit; it has a cut of its own
-        size_t sp_ = 0;
-        switch (h->N) {
-#define PSCASE(NN) \
-    case NN: sp_ = pair_smem<NN>(smem_bytes(h, true)); break;
-            PSCASE(1) PSCASE(2) PSCASE(3) PSCASE(4) PSCASE(5) PSCASE(6)
-#undef PSCASE
-        }
-        const char* pe = std::getenv("ALIPMPC_SPLIT_PAIR");
-        h->split_pair = !(pe && std::atoi(pe) == 0) && cfg->restoration == ALIPMPC_RESTORATION_IPOPT &&
-                        pair_ksm(h->mo4 / 4) && sp_ <= 160 * 1024;
-        if (h->split_pair && !std::getenv("ALIPMPC_SPLIT_IT") && SPLIT_IT_DEFAULT_RESTO_PAIR < h->cfg.max_iter)
-            h->split_it = SPLIT_IT_DEFAULT_RESTO_PAIR;
-    }
-    *handle = h;
-    return ALIPMPC_OK;
-}
-
-// A wave-program solve whose batch fits the resident slots (one wave per instance) runs as a SPLIT launch: phase 1
-// solves every instance for up to split_it iterations; an instance still running then writes its loop state to a
-// record and stops; phase 2 resumes those instances, one wave each.  The long instances (cfg2: 12 % run to the
-// 30-iteration cap) otherwise finish at the pace of the busiest SIMDs, which hold two or three of them
-// among their four waves; in phase 2 they are few enough for a SIMD each.  Every instance executes the same
-// arithmetic either way (the record holds its exact loop state): same bits (test_split_launch_bit_identical).
-// whether a solve of B instances with these cuts runs as a split launch (launch_solve and alipmpc_solve_launches share
-// it): the wave program (not DD), an iteration cut or — fp64, the team-capable build — a trial cut, B within the slots
-static bool split_form(const Handle* h, long long B, int split_it, int split_tr, long long slots)
-{
-    const alipmpc_cfg& cf = h->cfg;
-    if (cf.precision == ALIPMPC_PREC_FP32) split_tr = 0;   // (the team-capable build is fp64 only)
-    return cf.variant != ALIPMPC_VARIANT_DD && h->lane_nct < 0 && (split_it > 0 || split_tr > 0) && B >= 2 &&
-           B <= slots;
-}
-
-// the stream's record buffer (Handle::split), sized for `slots` instances; nullptr: run the one-phase form
-static void* split_buffer(Handle* h, hipStream_t st, size_t need, hipError_t& err)
-{
-    err = hipSuccess;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) return nullptr;
-    const bool capturing = cs != hipStreamCaptureStatusNone;
-    std::lock_guard<std::mutex> lk(h->split_mtx);
-    auto it = h->split.find(st);
-    if (it == h->split.end()) {
-        if (capturing) return nullptr;   // no allocation inside a capture: the one-phase form
-        // every buffer is kept until alipmpc_destroy (an eviction's hipFree synchronised the device and
-        // could free a buffer another thread had just been handed); a stream beyond SPLIT_STREAMS runs the one-phase
-        // form, which computes the same bits
-        // (the closed loop's own group streams do not count: ADVICE r5 — cycling user streams would otherwise leave
-        // its episode groups on the one-phase form)
-        bool group = false;
-        for (int g = 0; g < Handle::MAXG; ++g) group |= st != nullptr && st == h->gst[g];
-        size_t users = 0;
-        for (auto& kv : h->split) {
-            bool gk = false;
-            for (int g = 0; g < Handle::MAXG; ++g) gk |= kv.first != nullptr && kv.first == h->gst[g];
-            users += gk ? 0 : 1;
-        }
-        if (!group && users >= Handle::SPLIT_STREAMS) return nullptr;
-        Handle::SplitBuf sb;
-        if ((err = hipMalloc(&sb.p, need)) != hipSuccess) return nullptr;
-        sb.bytes = need;
-        it = h->split.emplace(st, sb).first;
-    }
-    if (it->second.bytes < need) return nullptr;   // (sized for the slots: does not happen)
-    return it->second.p;
-}
-
-// pair: the paired phase 2 where it applies (the batch API; the closed loop's per-tick solves keep the 4-wave form)
-static hipError_t launch_solve(Handle* h, const KP& P, hipStream_t st, int split_it, int split_tr, bool pair = false)
-{
-    const alipmpc_cfg& cf = h->cfg;
-    if (cf.precision == ALIPMPC_PREC_FP32) split_tr = 0;   // (the team-capable build is fp64 only)
-    if (!split_form(h, P.B, split_it, split_tr, 1ll << 62) || P.order) return launch(h, true, P, st);
-    unsigned res = 0;
-    if (hipError_t e = launch(h, true, P, st, &res)) return e;
-    const long long slots = (long long)res * WAVES_PER_BLOCK;
-    if (slots < P.B) return launch(h, true, P, st);   // the work-queue form
-    // records for the slots, not for this B: the buffer of a stream never changes size
-    const size_t rec_bytes = ((size_t)slots * ckpt_doubles(h->mo4) * sizeof(double) + 255) & ~(size_t)255;
-    const size_t hdr = (size_t)cont_hdr(slots);
-    // (instance ids and the two class lists of the single records)
-    const size_t need = rec_bytes + (hdr + (size_t)CONT_WORDS_PER_SLOT * (size_t)slots) * sizeof(uint32_t);
-    hipError_t berr = hipSuccess;
-    void* buf = split_buffer(h, st, need, berr);
-    if (berr != hipSuccess) return berr;
-    if (!buf) return launch(h, true, P, st);
-    uint32_t* cont = reinterpret_cast<uint32_t*>((char*)buf + rec_bytes);
-    if (hipError_t e = hipMemsetAsync(cont, 0, hdr * sizeof(uint32_t), st)) return e;
-    const int team = split_tr > 0 ? (int)std::min<long long>(P.B, TEAM_CAP) : 0;
-    KP P1 = P;
-    P1.ckpt_it = split_it > 0 ? split_it : 0;
-    P1.ckpt_tr = split_tr;
-    P1.team = team;
-    P1.ckpt = (double*)buf;
-    P1.cont = cont;
-    if (hipError_t e = launch(h, true, P1, st)) return e;
-    KP P2 = P;   // single records, and team records
-    P2.resume = pair && h->split_pair && team == 0 && cf.precision != ALIPMPC_PREC_FP32 ? 2 : 1;
-    P2.team = team;
-    P2.ckpt = (double*)buf;
-    P2.cont = cont;
-    return launch(h, true, P2, st);
-}
-
-static int run_batch(Handle* h, bool solve, int64_t B, const double* x0, const double* goal, const int8_t* leg,
-                     const double* cir, const int32_t* nc, const double* elp, const int32_t* ne, const double* u0,
-                     const double* last_u, double* u_out, double* foot_out, double* x_pred, int32_t* status, int32_t* iters, double* f,
-                     double* grad, double* c, double* J, double* cl, double* cu, double* goal_eff, int8_t* row_active,
-                     void* hip_stream)
-{
-    if (!h) return ALIPMPC_EINVAL;
-    if (B < 0) return fail(h, ALIPMPC_EINVAL, "B < 0");
-    if (B == 0) return ALIPMPC_OK;
-    const alipmpc_cfg& cf = h->cfg;
-    const bool dd = cf.variant == ALIPMPC_VARIANT_DD;
-    if (!x0 || !goal || (!leg && !dd) || !nc || !u0 || (cf.nc_max > 0 && !cir) || (cf.ne_max > 0 && (!elp || !ne)))
-        return fail(h, ALIPMPC_EINVAL, "missing input pointer");
-    if (solve && !u_out) return fail(h, ALIPMPC_EINVAL, "u_out is required");
-    if (solve && B >= (int64_t)1 << 31) return fail(h, ALIPMPC_EINVAL, "B >= 2^31 (32-bit work-queue counter)");
-    HIPCHK(h, hipSetDevice(h->device));
-    // host-facing u: the reference's 5N-vector (LIP) / 2N controls (DD); state dimension 5 / 3
-    const int N = h->N, n = dd ? 2 * N : 5 * N, sd = dd ? 3 : 5;
-    const size_t mm_ = (size_t)h->m_max;
-    KP P = make_kp(h, B, solve);
-    hipStream_t st = stream_of(h, hip_stream);
-    if (hip_stream) {
-        P.x0 = x0; P.goal = goal; P.leg = leg; P.cir = cir; P.nc = nc; P.elp = elp; P.ne = ne; P.u0 = u0;
-        P.last_u = last_u;
-        P.u_out = u_out; P.foot_out = foot_out; P.x_pred = x_pred; P.status = status; P.iters = iters;
-        P.f_out = f; P.grad_out = grad; P.c_out = c; P.J_out = J; P.cl_out = cl; P.cu_out = cu;
-        P.goal_eff_out = goal_eff; P.active_out = row_active;
-        const int ei = h->evi;
-        h->evi = (ei + 1) % Handle::NEV;
-        HIPCHK(h, hipEventRecord(h->ev[ei][0], st));
-        HIPCHK(h, solve ? launch_solve(h, P, st, h->split_it, h->split_tr, true) : launch(h, false, P, st));
-        HIPCHK(h, hipEventRecord(h->ev[ei][1], st));
-        h->evlast = ei;
-        h->timed = true;
-        return ALIPMPC_OK;
-    }
-    // host pointers: stage through the handle's device workspace (only the regions this call uses: the
-    // solve outputs for a solve, the eval outputs for an eval, J only when it is requested)
-    const size_t Bz = (size_t)B;
-    struct Stage {
-        double *x0, *goal, *cir, *elp, *u0, *lu, *u, *foot, *xp, *f, *g, *c, *J, *cl, *cu, *ge;
-        int8_t *leg, *ra;
-        int32_t *nc, *ne, *st, *it;
-    };
-    auto carve = [&](Carver& cv) {
-        Stage z{};
-        z.x0 = cv.take<double>(Bz * sd);
-        z.goal = cv.take<double>(Bz * 2);
-        z.leg = cv.take<int8_t>(Bz);
-        z.cir = cv.take<double>(Bz * 3 * cf.nc_max);
-        z.nc = cv.take<int32_t>(Bz);
-        z.elp = cv.take<double>(Bz * 5 * cf.ne_max);
-        z.ne = cv.take<int32_t>(Bz);
-        z.u0 = cv.take<double>(Bz * n);
-        z.lu = cv.take<double>(Bz * 2);
-        if (solve) {
-            z.u = cv.take<double>(Bz * n);
-            z.foot = cv.take<double>(Bz * 3);
-            z.xp = cv.take<double>(Bz * sd * N);
-            z.st = cv.take<int32_t>(Bz);
-            z.it = cv.take<int32_t>(Bz);
-        } else {
-            z.f = cv.take<double>(Bz);
-            z.g = cv.take<double>(Bz * n);
-            z.c = cv.take<double>(Bz * mm_);
-            if (J) z.J = cv.take<double>(Bz * mm_ * n);
-            z.cl = cv.take<double>(Bz * mm_);
-            z.cu = cv.take<double>(Bz * mm_);
-            z.ge = cv.take<double>(Bz * 2);
-            z.ra = cv.take<int8_t>(Bz * mm_);
-        }
-        return z;
-    };
-    size_t need = 0;
-    {
-        Carver cv{nullptr};
-        carve(cv);
-        need = cv.off + 256;
-    }
-    if (int e = ensure_stage(h, need)) return e;
-    Carver cv{(char*)h->stage};
-    const Stage z = carve(cv);
-    double *d_x0 = z.x0, *d_goal = z.goal, *d_cir = z.cir, *d_elp = z.elp, *d_u0 = z.u0, *d_lu = z.lu;
-    double *d_u = z.u, *d_foot = z.foot, *d_xp = z.xp, *d_f = z.f, *d_g = z.g, *d_c = z.c, *d_J = z.J;
-    double *d_cl = z.cl, *d_cu = z.cu, *d_ge = z.ge;
-    int8_t *d_leg = z.leg, *d_ra = z.ra;
-    int32_t *d_nc = z.nc, *d_ne = z.ne, *d_st = z.st, *d_it = z.it;
-    auto h2d = [&](void* d, const void* s, size_t bytes) { return hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, st); };
-    auto d2h = [&](void* d, const void* s, size_t bytes) { return hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToHost, st); };
-    HIPCHK(h, h2d(d_x0, x0, Bz * sd * 8));
-    HIPCHK(h, h2d(d_goal, goal, Bz * 2 * 8));
-    if (leg) HIPCHK(h, h2d(d_leg, leg, Bz));
-    if (cf.nc_max) HIPCHK(h, h2d(d_cir, cir, Bz * 3 * cf.nc_max * 8));
-    HIPCHK(h, h2d(d_nc, nc, Bz * 4));
-    if (cf.ne_max) {
-        HIPCHK(h, h2d(d_elp, elp, Bz * 5 * cf.ne_max * 8));
-        HIPCHK(h, h2d(d_ne, ne, Bz * 4));
-    }
-    HIPCHK(h, h2d(d_u0, u0, Bz * n * 8));
-    if (last_u) HIPCHK(h, h2d(d_lu, last_u, Bz * 2 * 8));
-    P.last_u = last_u ? d_lu : nullptr;
-    P.x0 = d_x0; P.goal = d_goal; P.leg = leg ? d_leg : nullptr; P.cir = d_cir; P.nc = d_nc;
-    P.elp = cf.ne_max ? d_elp : nullptr; P.ne = cf.ne_max ? d_ne : nullptr; P.u0 = d_u0;
-    if (solve) {
-        P.u_out = d_u; P.foot_out = d_foot; P.x_pred = d_xp; P.status = d_st; P.iters = d_it;
-    } else {
-        P.f_out = d_f; P.grad_out = d_g; P.c_out = d_c; P.J_out = J ? d_J : nullptr; P.cl_out = d_cl; P.cu_out = d_cu;
-        P.goal_eff_out = d_ge; P.active_out = d_ra;
-    }
-    const int ei = h->evi;
-    h->evi = (ei + 1) % Handle::NEV;
-    HIPCHK(h, hipEventRecord(h->ev[ei][0], st));
-    HIPCHK(h, solve ? launch_solve(h, P, st, h->split_it, h->split_tr, true) : launch(h, false, P, st));
-    HIPCHK(h, hipEventRecord(h->ev[ei][1], st));
-    h->evlast = ei;
-    h->timed = true;
-    if (solve) {
-        HIPCHK(h, d2h(u_out, d_u, Bz * n * 8));
-        if (foot_out) HIPCHK(h, d2h(foot_out, d_foot, Bz * 3 * 8));
-        if (x_pred) HIPCHK(h, d2h(x_pred, d_xp, Bz * sd * N * 8));
-        if (status) HIPCHK(h, d2h(status, d_st, Bz * 4));
-        if (iters) HIPCHK(h, d2h(iters, d_it, Bz * 4));
-    } else {
-        if (f) HIPCHK(h, d2h(f, d_f, Bz * 8));
-        if (grad) HIPCHK(h, d2h(grad, d_g, Bz * n * 8));
-        if (c) HIPCHK(h, d2h(c, d_c, Bz * mm_ * 8));
-        if (J) HIPCHK(h, d2h(J, d_J, Bz * mm_ * n * 8));
-        if (cl) HIPCHK(h, d2h(cl, d_cl, Bz * mm_ * 8));
-        if (cu) HIPCHK(h, d2h(cu, d_cu, Bz * mm_ * 8));
-        if (goal_eff) HIPCHK(h, d2h(goal_eff, d_ge, Bz * 2 * 8));
-        if (row_active) HIPCHK(h, d2h(row_active, d_ra, Bz * mm_));
-    }
-    HIPCHK(h, hipStreamSynchronize(st));
-    return ALIPMPC_OK;
-}
-
-int alipmpc_solve_batch(void* handle, int64_t B, const double* x0, const double* goal, const int8_t* leg,
-                        const double* cir, const int32_t* nc, const double* elp, const int32_t* ne, const double* u0,
-                        const double* last_u, double* u_out, double* foot_out, double* x_pred, int32_t* status,
-                        int32_t* iters, void* hip_stream)
-{
-    return run_batch((Handle*)handle, true, B, x0, goal, leg, cir, nc, elp, ne, u0, last_u, u_out, foot_out, x_pred, status,
-                     iters, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, hip_stream);
-}
-
-int alipmpc_eval_batch(void* handle, int64_t B, const double* x0, const double* goal, const int8_t* leg,
-                       const double* cir, const int32_t* nc, const double* elp, const int32_t* ne, const double* u,
-                       const double* last_u, double* f, double* grad, double* c, double* J, double* cl, double* cu,
-                       double* goal_eff, int8_t* row_active, void* hip_stream)
-{
-    return run_batch((Handle*)handle, false, B, x0, goal, leg, cir, nc, elp, ne, u, last_u, nullptr, nullptr, nullptr,
-                     nullptr, nullptr, f, grad, c, J, cl, cu, goal_eff, row_active, hip_stream);
-}
-
-int alipmpc_rollout_batch(void* handle, int64_t B, int32_t S, const double* x0, const double* goal, const int8_t* leg,
-                          const double* cir, const int32_t* nc, const double* elp, const int32_t* ne, const double* u0,
-                          const double* last_u, double* foot_traj, double* x_traj, int32_t* status_traj,
-                          int32_t* iters_traj, int32_t* steps_to_goal, double* u_traj, void* hip_stream)
-{
-    Handle* h = (Handle*)handle;
-    if (!h) return ALIPMPC_EINVAL;
-    if (B < 0 || S < 0) return fail(h, ALIPMPC_EINVAL, "B < 0 or S < 0");
-    if (B == 0 || S == 0) return ALIPMPC_OK;
-    const alipmpc_cfg& cf = h->cfg;
-    const bool dd = cf.variant == ALIPMPC_VARIANT_DD;
-    if (!x0 || !goal || (!leg && !dd) || !nc || !u0 || (cf.nc_max > 0 && !cir) || (cf.ne_max > 0 && (!elp || !ne)))
-        return fail(h, ALIPMPC_EINVAL, "missing input pointer");
-    HIPCHK(h, hipSetDevice(h->device));
-    const int N = h->N, n = dd ? 2 * N : 5 * N, sd = dd ? 3 : 5;
-    const size_t Bz = (size_t)B, Sz = (size_t)S;
-    hipStream_t st = stream_of(h, hip_stream);
-    const bool host = hip_stream == nullptr;   // ALIPMPC_STREAM_NULL: device pointers, null stream
-    // working set (+ staged inputs / outputs for host-pointer calls)
-    auto layout = [&](Carver& cv, bool take_io) {
-        struct L {
-            double *x, *u0, *lu, *u, *foot, *xp;
-            int8_t* leg;
-            int32_t *st, *it;
-            uint8_t* act;
-            double *goal, *cir, *elp, *ft, *xt, *ut;
-            int32_t *nc, *ne, *stt, *itt, *sg;
-        } l{};
-        l.x = cv.take<double>(Bz * sd); l.u0 = cv.take<double>(Bz * n); l.lu = cv.take<double>(Bz * 2);
-        l.u = cv.take<double>(Bz * n); l.foot = cv.take<double>(Bz * 3); l.xp = cv.take<double>(Bz * N * sd);
-        l.leg = cv.take<int8_t>(Bz); l.st = cv.take<int32_t>(Bz); l.it = cv.take<int32_t>(Bz);
-        l.act = cv.take<uint8_t>(Bz);
-        if (take_io) {
-            l.goal = cv.take<double>(Bz * 2); l.cir = cv.take<double>(Bz * 3 * cf.nc_max);
-            l.elp = cv.take<double>(Bz * 5 * cf.ne_max); l.nc = cv.take<int32_t>(Bz); l.ne = cv.take<int32_t>(Bz);
-            l.ft = cv.take<double>(Bz * Sz * 3); l.xt = cv.take<double>(Bz * (Sz + 1) * sd);
-            l.stt = cv.take<int32_t>(Bz * Sz); l.itt = cv.take<int32_t>(Bz * Sz); l.sg = cv.take<int32_t>(Bz);
-            if (u_traj) l.ut = cv.take<double>(Bz * Sz * n);
-        }
-        return l;
-    };
-    size_t need;
-    {
-        Carver cv{nullptr};
-        layout(cv, host);
-        need = cv.off + 256;
-    }
-    if (h->rstage_bytes < need) {
-        if (h->rstage) hipFree(h->rstage);
-        h->rstage = nullptr;
-        h->rstage_bytes = 0;
-        HIPCHK(h, hipMalloc(&h->rstage, need));
-        h->rstage_bytes = need;
-    }
-    Carver cv{(char*)h->rstage};
-    auto l = layout(cv, host);
-    const hipMemcpyKind in_kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    HIPCHK(h, hipMemcpyAsync(l.x, x0, Bz * sd * 8, in_kind, st));
-    HIPCHK(h, hipMemcpyAsync(l.u0, u0, Bz * n * 8, in_kind, st));
-    if (leg) HIPCHK(h, hipMemcpyAsync(l.leg, leg, Bz, in_kind, st));
-    if (last_u)
-        HIPCHK(h, hipMemcpyAsync(l.lu, last_u, Bz * 2 * 8, in_kind, st));
-    else
-        HIPCHK(h, hipMemsetAsync(l.lu, 0, Bz * 2 * 8, st));
-    const double *d_goal = goal, *d_cir = cir, *d_elp = elp;
-    const int32_t *d_nc = nc, *d_ne = ne;
-    double *d_ft = foot_traj, *d_xt = x_traj, *d_ut = u_traj;
-    int32_t *d_stt = status_traj, *d_itt = iters_traj, *d_sg = steps_to_goal;
-    if (host) {
-        HIPCHK(h, hipMemcpyAsync(l.goal, goal, Bz * 2 * 8, hipMemcpyHostToDevice, st));
-        if (cf.nc_max) HIPCHK(h, hipMemcpyAsync(l.cir, cir, Bz * 3 * cf.nc_max * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipMemcpyAsync(l.nc, nc, Bz * 4, hipMemcpyHostToDevice, st));
-        if (cf.ne_max) {
-            HIPCHK(h, hipMemcpyAsync(l.elp, elp, Bz * 5 * cf.ne_max * 8, hipMemcpyHostToDevice, st));
-            HIPCHK(h, hipMemcpyAsync(l.ne, ne, Bz * 4, hipMemcpyHostToDevice, st));
-        }
-        d_goal = l.goal; d_cir = l.cir; d_nc = l.nc;
-        d_elp = cf.ne_max ? l.elp : nullptr;
-        d_ne = cf.ne_max ? l.ne : nullptr;
-        d_ft = foot_traj ? l.ft : nullptr; d_xt = x_traj ? l.xt : nullptr;
-        d_stt = status_traj ? l.stt : nullptr; d_itt = iters_traj ? l.itt : nullptr;
-        d_sg = steps_to_goal ? l.sg : nullptr;
-        d_ut = u_traj ? l.ut : nullptr;
-    }
-    const unsigned g1 = (unsigned)((B + 255) / 256);
-    hipLaunchKernelGGL(rollout_init_kernel, dim3(g1), dim3(256), 0, st, (long long)B, (int)S, sd, (const double*)l.x,
-                       d_xt, l.act, d_sg);
-    HIPCHK(h, hipGetLastError());
-    KP P = make_kp(h, B, true);
-    P.goal = d_goal; P.cir = d_cir; P.nc = d_nc; P.elp = d_elp; P.ne = d_ne;
-    P.x0 = l.x; P.leg = dd ? nullptr : l.leg; P.u0 = l.u0; P.last_u = dd ? l.lu : nullptr; P.active = l.act;
-    P.u_out = l.u; P.foot_out = l.foot; P.x_pred = l.xp; P.status = l.st; P.iters = l.it;
-    AdvP A;
-    std::memset(&A, 0, sizeof(A));
-    A.B = B; A.S = S; A.N = N; A.sd = sd; A.n = n; A.variant = cf.variant; A.goal = d_goal;
-    A.x = l.x; A.u0 = l.u0; A.leg = l.leg; A.last_u = l.lu; A.u = l.u; A.foot = l.foot; A.x_pred = l.xp;
-    A.status = l.st; A.iters = l.it; A.active = l.act;
-    A.foot_traj = d_ft; A.x_traj = d_xt; A.status_traj = d_stt; A.iters_traj = d_itt; A.steps_to_goal = d_sg;
-    A.u_traj = d_ut;
-    const int ei = h->evi;
-    h->evi = (ei + 1) % Handle::NEV;
-    HIPCHK(h, hipEventRecord(h->ev[ei][0], st));
-    for (int t = 0; t < S; ++t) {
-        HIPCHK(h, launch(h, true, P, st));
-        A.t = t;
-        hipLaunchKernelGGL(advance_kernel, dim3(g1), dim3(256), 0, st, A);
-        HIPCHK(h, hipGetLastError());
-    }
-    HIPCHK(h, hipEventRecord(h->ev[ei][1], st));
-    h->evlast = ei;
-    h->timed = true;
-    if (host) {
-        if (foot_traj) HIPCHK(h, hipMemcpyAsync(foot_traj, l.ft, Bz * Sz * 3 * 8, hipMemcpyDeviceToHost, st));
-        if (x_traj) HIPCHK(h, hipMemcpyAsync(x_traj, l.xt, Bz * (Sz + 1) * sd * 8, hipMemcpyDeviceToHost, st));
-        if (status_traj) HIPCHK(h, hipMemcpyAsync(status_traj, l.stt, Bz * Sz * 4, hipMemcpyDeviceToHost, st));
-        if (iters_traj) HIPCHK(h, hipMemcpyAsync(iters_traj, l.itt, Bz * Sz * 4, hipMemcpyDeviceToHost, st));
-        if (steps_to_goal) HIPCHK(h, hipMemcpyAsync(steps_to_goal, l.sg, Bz * 4, hipMemcpyDeviceToHost, st));
-        if (u_traj) HIPCHK(h, hipMemcpyAsync(u_traj, l.ut, Bz * Sz * n * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipStreamSynchronize(st));
-    }
-    return ALIPMPC_OK;
-}
-
-// the dataset end of alipmpc_closed_loop_dataset_batch (nullptr: alipmpc_closed_loop_batch)
-struct DsArgs {
-    int64_t first_index;
-    double safe_dis;
-    int64_t max_rows;
-    double *X, *y_mpc, *y_act;
-    int32_t* row_status;
-    int64_t* row_start;
-};
-
-// both closed-loop entry points.  Without ds the launches, grouping, workspace layout and results are those of
-// alipmpc_closed_loop_batch as it always was: everything the dataset adds is carved after the existing areas and
-// sits behind a test of ds or of a staging pointer.
-static int closed_loop_impl(Handle* h, int64_t B, int32_t S, int32_t f_cyc, double kick, uint64_t seed,
-                            const double* x0, const double* foot0, const double* goal, const int8_t* leg,
-                            const double* cir, const int32_t* nc, const double* elp, const int32_t* ne,
-                            double* foot_traj, double* x_traj, double* hd_traj, int32_t* status_traj,
-                            int32_t* iters_traj, int32_t* steps_to_goal, double* action_traj, void* hip_stream,
-                            const DsArgs* ds)
-{
-    if (!h) return ALIPMPC_EINVAL;
-    const alipmpc_cfg& cf = h->cfg;
-    if (cf.variant == ALIPMPC_VARIANT_DD) return fail(h, ALIPMPC_EUNSUPPORTED, "closed loop: LIP variants only");
-    if (B < 0 || S < 0 || f_cyc < 1 || !(kick >= 0)) return fail(h, ALIPMPC_EINVAL, "B, S < 0, f_cyc < 1 or kick < 0");
-    const int ncx = 3 * cf.nc_max + 5 * cf.ne_max + 11;   // columns of X
-    if (ds) {
-        if (ds->first_index < 0 || ds->first_index > (int64_t)1 << 32 || ds->first_index + B > (int64_t)1 << 32)
-            return fail(h, ALIPMPC_EINVAL, "closed loop dataset: first_index < 0 or first_index + B > 2^32");
-        if (!(ds->safe_dis >= 0) || !std::isfinite(ds->safe_dis))
-            return fail(h, ALIPMPC_EINVAL, "closed loop dataset: safe_dis negative or not finite");
-        if (ds->max_rows < 0) return fail(h, ALIPMPC_EINVAL, "closed loop dataset: max_rows < 0");
-        if ((long long)S * f_cyc * ncx > 0x7fffffffLL)
-            return fail(h, ALIPMPC_EINVAL, "closed loop dataset: S * f_cyc * columns of X > 2^31 - 1");
-        if (B == 0 || S == 0) {   // no rows: row_start is all zero
-            if (ds->row_start) {
-                if (hip_stream == nullptr) {
-                    std::memset(ds->row_start, 0, ((size_t)B + 1) * 8);
-                } else {
-                    HIPCHK(h, hipSetDevice(h->device));
-                    HIPCHK(h, hipMemsetAsync(ds->row_start, 0, ((size_t)B + 1) * 8, stream_of(h, hip_stream)));
-                }
-            }
-            return ALIPMPC_OK;
-        }
-    }
-    if (B == 0 || S == 0) return ALIPMPC_OK;
-    if (!x0 || !foot0 || !goal || !leg || !nc || (cf.nc_max > 0 && !cir) || (cf.ne_max > 0 && (!elp || !ne)))
-        return fail(h, ALIPMPC_EINVAL, "missing input pointer");
-    HIPCHK(h, hipSetDevice(h->device));
-    const int N = h->N, n = 5 * N;
-    const size_t Bz = (size_t)B, Sz = (size_t)S, Fz = (size_t)f_cyc;
-    hipStream_t st = stream_of(h, hip_stream);
-    const bool host = hip_stream == nullptr;
-    // dataset: are rows wanted (or row_start alone), and the rows the host-mode copies of the row arrays hold
-    const bool ds_rows = ds && (ds->X || ds->y_mpc || ds->y_act || ds->row_status);
-    const size_t ds_cap = ds ? std::min<size_t>((size_t)ds->max_rows, Bz * Sz * Fz) : 0;
-    auto layout = [&](Carver& cv, bool take_io) {
-        struct L {
-            double *x, *pst, *hdv, *mhd, *plan, *xs, *u0, *u, *foot, *xp;
-            int8_t *leg, *sleg;
-            uint8_t *flags, *act;
-            int32_t *st, *it, *ord;
-            double *goal, *cir, *elp, *ft, *xt, *hd, *actd;
-            int32_t *nc, *ne, *stt, *itt, *sg;
-            double *vdes, *pose0;
-            double *ds_tick, *ds_step, *dX, *dym, *dya;
-            int32_t *ds_nst, *drs;
-            long long* ds_rs;
-        } l{};
-        l.vdes = cv.take<double>(Bz * 2); l.pose0 = cv.take<double>(Bz * 3);
-        l.x = cv.take<double>(Bz * 5); l.pst = cv.take<double>(Bz * 2); l.hdv = cv.take<double>(Bz * 4);
-        l.mhd = cv.take<double>(Bz * 3); l.plan = cv.take<double>(Bz * n); l.xs = cv.take<double>(Bz * 5);
-        l.u0 = cv.take<double>(Bz * n); l.u = cv.take<double>(Bz * n); l.foot = cv.take<double>(Bz * 3);
-        l.xp = cv.take<double>(Bz * n); l.leg = cv.take<int8_t>(Bz); l.sleg = cv.take<int8_t>(Bz);
-        l.flags = cv.take<uint8_t>(Bz); l.act = cv.take<uint8_t>(Bz); l.st = cv.take<int32_t>(Bz);
-        l.it = cv.take<int32_t>(Bz); l.ord = cv.take<int32_t>(Bz);
-        if (take_io) {
-            l.goal = cv.take<double>(Bz * 2); l.cir = cv.take<double>(Bz * 3 * cf.nc_max);
-            l.elp = cv.take<double>(Bz * 5 * cf.ne_max); l.nc = cv.take<int32_t>(Bz); l.ne = cv.take<int32_t>(Bz);
-            l.ft = cv.take<double>(Bz * Sz * 3); l.xt = cv.take<double>(Bz * (Sz + 1) * 5);
-            l.hd = cv.take<double>(Bz * Sz * 2); l.stt = cv.take<int32_t>(Bz * Sz * Fz);
-            l.itt = cv.take<int32_t>(Bz * Sz * Fz); l.sg = cv.take<int32_t>(Bz);
-            if (action_traj) l.actd = cv.take<double>(Bz * Sz * Fz * 8);
-        }
-        if (ds) {   // after everything the existing call carves
-            l.ds_rs = cv.take<long long>(Bz + 1);
-            l.ds_nst = cv.take<int32_t>(Bz);
-            if (ds_rows) {
-                l.ds_step = cv.take<double>(Bz * Sz * DS_STEP);
-                l.ds_tick = cv.take<double>(Bz * Sz * Fz * DS_TICK);
-                if (!take_io && ds->row_status && !status_traj) l.stt = cv.take<int32_t>(Bz * Sz * Fz);
-                if (take_io) {
-                    if (ds->X) l.dX = cv.take<double>(ds_cap * (size_t)ncx);
-                    if (ds->y_mpc) l.dym = cv.take<double>(ds_cap * 8);
-                    if (ds->y_act) l.dya = cv.take<double>(ds_cap * 8);
-                    if (ds->row_status) l.drs = cv.take<int32_t>(ds_cap);
-                }
-            }
-        }
-        return l;
-    };
-    size_t need;
-    {
-        Carver cv{nullptr};
-        layout(cv, host);
-        need = cv.off + 256;
-    }
-    if (h->rstage_bytes < need) {
-        if (h->rstage) hipFree(h->rstage);
-        h->rstage = nullptr;
-        h->rstage_bytes = 0;
-        if (hipError_t e = hipMalloc(&h->rstage, need); e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(h, ALIPMPC_EHIP, "closed loop: workspace of " + std::to_string(need) + " bytes" +
-                        (ds_rows ? " (row staging " + std::to_string(Bz * Sz * Fz * DS_TICK * 8) + " bytes)" : "") +
-                        ": " + hipGetErrorString(e));
-        }
-        h->rstage_bytes = need;
-    }
-    Carver cv{(char*)h->rstage};
-    auto l = layout(cv, host);
-    const hipMemcpyKind in_kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    HIPCHK(h, hipMemcpyAsync(l.x, x0, Bz * 5 * 8, in_kind, st));
-    HIPCHK(h, hipMemcpyAsync(l.pst, foot0, Bz * 2 * 8, in_kind, st));
-    HIPCHK(h, hipMemcpyAsync(l.leg, leg, Bz, in_kind, st));
-    const double *d_goal = goal, *d_cir = cir, *d_elp = elp;
-    const int32_t *d_nc = nc, *d_ne = ne;
-    double *d_ft = foot_traj, *d_xt = x_traj, *d_hd = hd_traj;
-    int32_t *d_stt = status_traj, *d_itt = iters_traj, *d_sg = steps_to_goal;
-    double* d_act = action_traj;
-    if (host) {
-        HIPCHK(h, hipMemcpyAsync(l.goal, goal, Bz * 2 * 8, hipMemcpyHostToDevice, st));
-        if (cf.nc_max) HIPCHK(h, hipMemcpyAsync(l.cir, cir, Bz * 3 * cf.nc_max * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipMemcpyAsync(l.nc, nc, Bz * 4, hipMemcpyHostToDevice, st));
-        if (cf.ne_max) {
-            HIPCHK(h, hipMemcpyAsync(l.elp, elp, Bz * 5 * cf.ne_max * 8, hipMemcpyHostToDevice, st));
-            HIPCHK(h, hipMemcpyAsync(l.ne, ne, Bz * 4, hipMemcpyHostToDevice, st));
-        }
-        d_goal = l.goal; d_cir = l.cir; d_nc = l.nc;
-        d_elp = cf.ne_max ? l.elp : nullptr;
-        d_ne = cf.ne_max ? l.ne : nullptr;
-        d_ft = foot_traj ? l.ft : nullptr; d_xt = x_traj ? l.xt : nullptr; d_hd = hd_traj ? l.hd : nullptr;
-        d_stt = status_traj ? l.stt : nullptr; d_itt = iters_traj ? l.itt : nullptr;
-        d_sg = steps_to_goal ? l.sg : nullptr;
-        d_act = action_traj ? l.actd : nullptr;
-    }
-    if (ds_rows && ds->row_status && !d_stt) d_stt = l.stt;   // row_status is compacted from the ticks' statuses
-    CLP C;
-    std::memset(&C, 0, sizeof(C));
-    C.B = B; C.S = S; C.f = f_cyc; C.variant = cf.variant; C.N = N; C.kick = kick; C.seed = (unsigned long long)seed;
-    C.goal = d_goal; C.x = l.x; C.pst = l.pst; C.hdv = l.hdv; C.mhd = l.mhd; C.plan = l.plan; C.leg = l.leg;
-    C.flags = l.flags; C.xs = l.xs; C.u0 = l.u0; C.sleg = l.sleg; C.u = l.u; C.foot = l.foot; C.x_pred = l.xp;
-    C.status = l.st; C.iters = l.it; C.active = l.act;
-    C.foot_traj = d_ft; C.x_traj = d_xt; C.hd_traj = d_hd; C.status_traj = d_stt; C.iters_traj = d_itt;
-    C.steps_to_goal = d_sg;
-    C.action_traj = d_act; C.vdes = l.vdes; C.pose0 = l.pose0;
-    C.ds_tick = l.ds_tick; C.ds_step = l.ds_step; C.ds_nst = l.ds_nst;
-    const double beta = std::sqrt(cf.g / cf.H), T = cf.dt, dt = T / f_cyc;
-    {   // alip_des_vel(0.6, leg_ind) (MPC_LIP_modi.py:181-186)
-        const double sh = std::sinh(beta * T), ch = std::cosh(beta * T);
-        C.vdx = beta / std::tanh(T * beta / 2) * 0.6 * T / 2;
-        C.vdy0 = (beta * sh) / (ch + 1);
-    }
-    C.ch_d = std::cosh(beta * dt); C.shb_d = std::sinh(beta * dt) / beta; C.bsh_d = std::sinh(beta * dt) * beta;
-    C.td = dt / T;
-    const unsigned g1 = (unsigned)((B + 255) / 256);
-    hipLaunchKernelGGL(cl_init_kernel, dim3(g1), dim3(256), 0, st, C);
-    HIPCHK(h, hipGetLastError());
-    KP P = make_kp(h, B, true);
-    P.goal = d_goal; P.cir = d_cir; P.nc = d_nc; P.elp = d_elp; P.ne = d_ne;
-    P.x0 = l.xs; P.leg = l.sleg; P.u0 = l.u0; P.active = l.act;
-    P.u_out = l.u; P.foot_out = l.foot; P.x_pred = l.xp; P.status = l.st; P.iters = l.it;
-    // longest-first launch order of each tick (wave program; opt-in, ALIPMPC_CL_ORDER=1): it puts at most one long
-    // instance on a SIMD, but a tick's time is set by its single slowest instance, a warm-started one whose line
-    // search halves ~20 times per iteration (tools/cl_wstamps.py, profiles/r3/wst): 52.13 vs 52.00 ms per loop
-    const char* oe = std::getenv("ALIPMPC_CL_ORDER");
-    const bool order_ok = cf.program != ALIPMPC_PROGRAM_LANE && oe && std::strcmp(oe, "1") == 0;
-    // Episode groups (ALIPMPC_CL_GROUPS, >= 256 episodes each): contiguous ranges of episodes whose ticks run on
-    // streams of their own, so a tick that waits on one slow instance holds back only its group; the other groups'
-    // launches fill the device meanwhile.  Every episode runs the same kernels on the same values (the kick is seeded
-    // by the global episode index), so the outputs do not depend on the grouping (GPU test).
-    int G = env_groups();
-#ifdef ALIP_WSTAMP
-    G = 1;   // (diagnostic records are indexed by the whole batch)
-#endif
-    if (order_ok) G = 1;   // (the opt-in launch order is a permutation of the whole batch)
-    G = (int)std::max<long long>(1, std::min<long long>({(long long)G, (long long)Handle::MAXG, B / 256}));
-    struct Grp {
-        CLP C;
-        KP P;
-        hipStream_t s;
-        unsigned g1;
-    } grp[Handle::MAXG];
-    const long long nn = n, SF = (long long)S * f_cyc;
-    for (int g = 0; g < G; ++g) {
-        const long long b0 = B * g / G, Bg = B * (g + 1) / G - b0;
-        auto o = [&](auto& p, long long per) {
-            if (p) p += b0 * per;
-        };
-        CLP c = C;
-        c.B = Bg;
-        c.b0 = (ds ? (long long)ds->first_index : 0) + b0;
-        o(c.goal, 2); o(c.x, 5); o(c.pst, 2); o(c.hdv, 4); o(c.mhd, 3); o(c.plan, nn); o(c.leg, 1); o(c.flags, 1);
-        o(c.xs, 5); o(c.u0, nn); o(c.sleg, 1); o(c.u, nn); o(c.foot, 3); o(c.x_pred, nn); o(c.status, 1);
-        o(c.iters, 1); o(c.active, 1); o(c.foot_traj, 3LL * S); o(c.x_traj, 5LL * (S + 1)); o(c.hd_traj, 2LL * S);
-        o(c.status_traj, SF); o(c.iters_traj, SF); o(c.steps_to_goal, 1); o(c.action_traj, 8 * SF); o(c.vdes, 2);
-        o(c.pose0, 3);
-        o(c.ds_tick, DS_TICK * SF); o(c.ds_step, (long long)DS_STEP * S); o(c.ds_nst, 1);
-        KP q = P;
-        q.B = Bg;
-        o(q.goal, 2); o(q.cir, 3LL * cf.nc_max); o(q.nc, 1); o(q.elp, 5LL * cf.ne_max); o(q.ne, 1); o(q.x0, 5);
-        o(q.leg, 1); o(q.u0, nn); o(q.active, 1); o(q.u_out, nn); o(q.foot_out, 3); o(q.x_pred, nn); o(q.status, 1);
-        o(q.iters, 1);
-        grp[g].C = c;
-        grp[g].P = q;
-        grp[g].g1 = (unsigned)((Bg + 255) / 256);
-        grp[g].s = st;
-        if (G > 1) {
-            if (!h->gst[g]) HIPCHK(h, hipStreamCreateWithFlags(&h->gst[g], hipStreamNonBlocking));
-            if (!h->gev[g]) HIPCHK(h, hipEventCreateWithFlags(&h->gev[g], hipEventDisableTiming));
-            grp[g].s = h->gst[g];
-        }
-    }
-    if (G > 1 && !h->gev[Handle::MAXG]) HIPCHK(h, hipEventCreateWithFlags(&h->gev[Handle::MAXG], hipEventDisableTiming));
-    const int ei = h->evi;
-    h->evi = (ei + 1) % Handle::NEV;
-    HIPCHK(h, hipEventRecord(h->ev[ei][0], st));
-    if (G > 1) {   // fork
-        HIPCHK(h, hipEventRecord(h->gev[Handle::MAXG], st));
-        for (int g = 0; g < G; ++g) HIPCHK(h, hipStreamWaitEvent(grp[g].s, h->gev[Handle::MAXG], 0));
-    }
-    for (int s = 0; s < S; ++s) {
-        for (int i = 0; i < f_cyc; ++i) {
-            // rest_t = step_t - i * (step_t / f_cyc)   (main_sim_mpc.py:78)
-            const double rest = T - i * (T / f_cyc);
-            for (int g = 0; g < G; ++g) {
-                CLP& Cg = grp[g].C;
-                KP& Pg = grp[g].P;
-                const hipStream_t sg = grp[g].s;
-                Cg.s = s;
-                Cg.i = i;
-                Cg.ch_r = std::cosh(beta * rest); Cg.shb_r = std::sinh(beta * rest) / beta;
-                Cg.bsh_r = std::sinh(beta * rest) * beta; Cg.tr = rest * (1.0 / T);
-                hipLaunchKernelGGL(cl_project_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Cg);
-                HIPCHK(h, hipGetLastError());
-                // wave program: after the first tick, solve last tick's long instances first (same bits per instance)
-                Pg.order = nullptr;
-                if (order_ok && (s > 0 || i > 0)) {
-                    hipLaunchKernelGGL(cl_order_kernel, dim3(1), dim3(CL_ORDER_THREADS), 0, sg, (const int32_t*)l.it,
-                                       (const uint8_t*)l.act, (long long)B, l.ord);
-                    HIPCHK(h, hipGetLastError());
-                    Pg.order = l.ord;
-                }
-                // each group's own counter pair (after the ring): its launches run in order on its stream, and no
-                // other group or call can take the pair while one of them is in flight (ring pairs taken
-                // per tick let a group running ticks ahead land on a pair another group's launch still used)
-                Pg.queue = h->dq + 2 * (Handle::NQ + g);
-#ifdef ALIP_WSTAMP
-                {   // diagnostic record slots of this tick: (s f_cyc + i) B + instance
-                    const long long base = ((long long)s * f_cyc + i) * B;
-                    HIPCHK(h, hipMemcpyToSymbolAsync(HIP_SYMBOL(alip::g_wstamp_base), &base, sizeof(base), 0,
-                                                     hipMemcpyHostToDevice, sg));
-                    HIPCHK(h, hipStreamSynchronize(sg));   // &base is a stack value
-                }
-#endif
-                HIPCHK(h, launch_solve(h, Pg, sg, h->cl_split_it, h->cl_split_tr));
-                hipLaunchKernelGGL(cl_update_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Cg);
-                HIPCHK(h, hipGetLastError());
-            }
-        }
-    }
-    if (G > 1) {   // join
-        for (int g = 0; g < G; ++g) {
-            HIPCHK(h, hipEventRecord(h->gev[g], grp[g].s));
-            HIPCHK(h, hipStreamWaitEvent(st, h->gev[g], 0));
-        }
-    }
-    long long* d_rs = nullptr;
-    if (ds) {   // rows: scan the steps entered into row_start, then one wavefront per episode compacts its rows
-        d_rs = host || !ds->row_start ? l.ds_rs : (long long*)ds->row_start;
-        hipLaunchKernelGGL(ds_scan_kernel, dim3(1), dim3(DS_SCAN_THREADS), 0, st, (const int32_t*)l.ds_nst,
-                           (long long)B, (int)f_cyc, d_rs);
-        HIPCHK(h, hipGetLastError());
-        if (ds_rows && ds->max_rows > 0) {
-            DsP D;
-            std::memset(&D, 0, sizeof(D));
-            D.B = B; D.max_rows = ds->max_rows; D.S = S; D.f = f_cyc; D.nc_max = cf.nc_max; D.ne_max = cf.ne_max;
-            D.safe = ds->safe_dis; D.T = T; D.Td = T / f_cyc;
-            D.tick = l.ds_tick; D.step = l.ds_step; D.stt = d_stt;
-            D.cir = d_cir; D.nc = d_nc; D.elp = d_elp; D.ne = d_ne; D.goal = d_goal; D.row_start = d_rs;
-            D.X = host ? l.dX : ds->X; D.y_mpc = host ? l.dym : ds->y_mpc; D.y_act = host ? l.dya : ds->y_act;
-            D.row_status = host ? l.drs : ds->row_status;
-            constexpr int WPB = 256 / WAVE;
-            hipLaunchKernelGGL(ds_compact_kernel, dim3((unsigned)((B + WPB - 1) / WPB)), dim3(256), 0, st, D);
-            HIPCHK(h, hipGetLastError());
-        }
-    }
-    HIPCHK(h, hipEventRecord(h->ev[ei][1], st));
-    h->evlast = ei;
-    h->timed = true;
-    if (host && ds) {   // the total first: only the rows that exist (and fit) are copied back
-        std::vector<long long> rs(Bz + 1);
-        HIPCHK(h, hipMemcpyAsync(rs.data(), d_rs, (Bz + 1) * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipStreamSynchronize(st));
-        if (ds->row_start) std::memcpy(ds->row_start, rs.data(), (Bz + 1) * 8);
-        const size_t nr = std::min<size_t>((size_t)rs[Bz], ds_cap);
-        if (nr && ds->X) HIPCHK(h, hipMemcpyAsync(ds->X, l.dX, nr * ncx * 8, hipMemcpyDeviceToHost, st));
-        if (nr && ds->y_mpc) HIPCHK(h, hipMemcpyAsync(ds->y_mpc, l.dym, nr * 8 * 8, hipMemcpyDeviceToHost, st));
-        if (nr && ds->y_act) HIPCHK(h, hipMemcpyAsync(ds->y_act, l.dya, nr * 8 * 8, hipMemcpyDeviceToHost, st));
-        if (nr && ds->row_status) HIPCHK(h, hipMemcpyAsync(ds->row_status, l.drs, nr * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (host) {
-        if (foot_traj) HIPCHK(h, hipMemcpyAsync(foot_traj, l.ft, Bz * Sz * 3 * 8, hipMemcpyDeviceToHost, st));
-        if (x_traj) HIPCHK(h, hipMemcpyAsync(x_traj, l.xt, Bz * (Sz + 1) * 5 * 8, hipMemcpyDeviceToHost, st));
-        if (hd_traj) HIPCHK(h, hipMemcpyAsync(hd_traj, l.hd, Bz * Sz * 2 * 8, hipMemcpyDeviceToHost, st));
-        if (action_traj) HIPCHK(h, hipMemcpyAsync(action_traj, l.actd, Bz * Sz * Fz * 8 * 8, hipMemcpyDeviceToHost, st));
-        if (status_traj) HIPCHK(h, hipMemcpyAsync(status_traj, l.stt, Bz * Sz * Fz * 4, hipMemcpyDeviceToHost, st));
-        if (iters_traj) HIPCHK(h, hipMemcpyAsync(iters_traj, l.itt, Bz * Sz * Fz * 4, hipMemcpyDeviceToHost, st));
-        if (steps_to_goal) HIPCHK(h, hipMemcpyAsync(steps_to_goal, l.sg, Bz * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipStreamSynchronize(st));
-    }
-    return ALIPMPC_OK;
-}
-
-int alipmpc_closed_loop_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc, double kick, uint64_t seed,
-                              const double* x0, const double* foot0, const double* goal, const int8_t* leg,
-                              const double* cir, const int32_t* nc, const double* elp, const int32_t* ne,
-                              double* foot_traj, double* x_traj, double* hd_traj, int32_t* status_traj,
-                              int32_t* iters_traj, int32_t* steps_to_goal, double* action_traj, void* hip_stream)
-{
-    return closed_loop_impl((Handle*)handle, B, S, f_cyc, kick, seed, x0, foot0, goal, leg, cir, nc, elp, ne, foot_traj,
-                            x_traj, hd_traj, status_traj, iters_traj, steps_to_goal, action_traj, hip_stream, nullptr);
-}
-
-int alipmpc_closed_loop_dataset_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc, double kick, uint64_t seed,
-                                      const double* x0, const double* foot0, const double* goal, const int8_t* leg,
-                                      const double* cir, const int32_t* nc, const double* elp, const int32_t* ne,
-                                      double* foot_traj, double* x_traj, double* hd_traj, int32_t* status_traj,
-                                      int32_t* iters_traj, int32_t* steps_to_goal, double* action_traj,
-                                      int64_t first_index, double safe_dis, int64_t max_rows, double* X, double* y_mpc,
-                                      double* y_act, int32_t* row_status, int64_t* row_start, void* hip_stream)
-{
-    const DsArgs ds{first_index, safe_dis, max_rows, X, y_mpc, y_act, row_status, row_start};
-    return closed_loop_impl((Handle*)handle, B, S, f_cyc, kick, seed, x0, foot0, goal, leg, cir, nc, elp, ne, foot_traj,
-                            x_traj, hd_traj, status_traj, iters_traj, steps_to_goal, action_traj, hip_stream, &ds);
-}
-
-int32_t alipmpc_trace_len(const alipmpc_cfg* cfg)
-{
-    if (!cfg || cfg->variant == ALIPMPC_VARIANT_DD || !(cfg->dt > 0)) return 0;
-    // numpy arange length: ceil((stop - start) / step) with stop = dt + 0.01, step = 0.01; + the x_k row
-    return 1 + (int32_t)std::ceil((cfg->dt + 0.01) / 0.01);
-}
-
-int alipmpc_trace_batch(void* handle, int64_t B, const double* x0, const double* u, double* trace, void* hip_stream)
-{
-    Handle* h = (Handle*)handle;
-    if (!h) return ALIPMPC_EINVAL;
-    const alipmpc_cfg& cf = h->cfg;
-    if (cf.variant == ALIPMPC_VARIANT_DD) return fail(h, ALIPMPC_EUNSUPPORTED, "trace: LIP variants only");
-    if (B < 0) return fail(h, ALIPMPC_EINVAL, "B < 0");
-    if (B == 0) return ALIPMPC_OK;
-    if (!x0 || !u || !trace) return fail(h, ALIPMPC_EINVAL, "missing pointer");
-    HIPCHK(h, hipSetDevice(h->device));
-    const int N = h->N, rows = alipmpc_trace_len(&cf);
-    const size_t Bz = (size_t)B, nout = Bz * N * rows * 2;
-    TrP T;
-    std::memset(&T, 0, sizeof(T));
-    T.B = B; T.N = N; T.rows = rows; T.step = 0.01;
-    T.beta = std::sqrt(cf.g / cf.H);
-    {
-        const double b = T.beta, dT = cf.dt, ch = std::cosh(b * dT), sh = std::sinh(b * dT);
-        const double A[25] = {ch, 0, sh / b, 0, 0, 0, ch, 0, sh / b, 0, sh * b, 0, ch, 0, 0,
-                              0, sh * b, 0, ch, 0, 0, 0, 0, 0, 1};
-        const double Bm[15] = {1 - ch, 0, 0, 0, 1 - ch, 0, -sh * b, 0, 0, 0, -sh * b, 0, 0, 0, 1};
-        const double Dd = 5.0 * (ch - 1) * (ch - 1) + (sh * b) * (sh * b);
-        const double Ch = -5.0 * (ch - 1) / Dd, Sh = -sh * b / Dd;
-        const double W[15] = {Ch, 0, Sh, 0, 0, 0, Ch, 0, Sh, 0, 0, 0, 0, 0, 1};
-        double BWA[25];
-        std::memcpy(T.A, A, sizeof(A));
-        std::memcpy(T.W, W, sizeof(W));
-        mm(Bm, W, T.MB, 5, 3, 5);
-        mm(T.MB, A, BWA, 5, 5, 5);
-        for (int i = 0; i < 25; ++i) T.MA[i] = A[i] - BWA[i];
-    }
-    hipStream_t st = stream_of(h, hip_stream);
-    const bool host = hip_stream == nullptr;
-    if (host) {
-        const size_t bytes = Bz * 5 * 8 + Bz * 5 * N * 8 + nout * 8 + 512;
-        if (int rc = ensure_stage(h, bytes)) return rc;
-        Carver cv{(char*)h->stage};
-        double* dx = cv.take<double>(Bz * 5);
-        double* du = cv.take<double>(Bz * 5 * N);
-        double* dt_ = cv.take<double>(nout);
-        HIPCHK(h, hipMemcpyAsync(dx, x0, Bz * 5 * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipMemcpyAsync(du, u, Bz * 5 * N * 8, hipMemcpyHostToDevice, st));
-        T.x0 = dx; T.u = du; T.trace = dt_;
-    } else {
-        T.x0 = x0; T.u = u; T.trace = trace;
-    }
-    const long long total = (long long)B * N * rows;
-    hipLaunchKernelGGL(trace_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, T);
-    HIPCHK(h, hipGetLastError());
-    if (host) {
-        HIPCHK(h, hipMemcpyAsync(trace, T.trace, nout * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipStreamSynchronize(st));
-    }
-    return ALIPMPC_OK;
-}
-
-int32_t alipmpc_audit_summary_len(int32_t n_edges)
-{
-    if (n_edges < 0 || n_edges > ALIPMPC_AUDIT_MAX_EDGES) return ALIPMPC_EINVAL;
-    return AU_HEAD + (n_edges + 1) + AU_CROSS;
-}
-
-int alipmpc_audit_batch(void* handle, int64_t B, const double* x0, const double* goal, const int8_t* leg,
-                        const double* cir, const int32_t* nc, const double* elp, const int32_t* ne, const double* u,
-                        const int32_t* status, double* metrics, int32_t* where, double viol_tol, const double* edges,
-                        int32_t n_edges, int64_t* summary, void* hip_stream)
-{
-    Handle* h = (Handle*)handle;
-    if (!h) return ALIPMPC_EINVAL;
-    const alipmpc_cfg& cf = h->cfg;
-    if (cf.variant == ALIPMPC_VARIANT_DD) return fail(h, ALIPMPC_EUNSUPPORTED, "audit: LIP variants only");
-    if (B < 0) return fail(h, ALIPMPC_EINVAL, "B < 0");
-    if (n_edges < 0 || n_edges > ALIPMPC_AUDIT_MAX_EDGES)
-        return fail(h, ALIPMPC_EINVAL, "audit: n_edges outside [0, ALIPMPC_AUDIT_MAX_EDGES]");
-    if (n_edges > 0 && !edges) return fail(h, ALIPMPC_EINVAL, "audit: edges is NULL");
-    for (int i = 0; i < n_edges; ++i)
-        if (!std::isfinite(edges[i]) || (i > 0 && !(edges[i] > edges[i - 1])))
-            return fail(h, ALIPMPC_EINVAL, "audit: edges must be finite and strictly increasing");
-    if (!std::isfinite(viol_tol) || viol_tol < 0) return fail(h, ALIPMPC_EINVAL, "audit: viol_tol must be finite and >= 0");
-    if (!u) return fail(h, ALIPMPC_EINVAL, "audit: u is NULL");
-    if (!metrics && !where && !summary) return fail(h, ALIPMPC_EINVAL, "audit: no output requested");
-    if (!x0 || !goal || !leg || !nc || (cf.nc_max > 0 && !cir) || (cf.ne_max > 0 && (!elp || !ne)))
-        return fail(h, ALIPMPC_EINVAL, "missing input pointer");
-    if (!h->dau) return fail(h, ALIPMPC_EUNSUPPORTED, "audit: the plan has no dense trace (dt <= 0)");
-    if (B == 0) return ALIPMPC_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    const int N = h->N, nu = 5 * N;
-    const size_t Bz = (size_t)B, ncm = (size_t)cf.nc_max, nem = (size_t)cf.ne_max;
-    const size_t nsum = (size_t)alipmpc_audit_summary_len(n_edges);
-    AuP A;
-    std::memset(&A, 0, sizeof(A));
-    A.kp = make_kp(h, B, false);
-    A.N = N;
-    A.rows = alipmpc_trace_len(&cf);
-    A.n_edges = n_edges;
-    A.has_status = status != nullptr;
-    A.tab = h->dau;
-    A.viol_tol = viol_tol;
-    for (int i = 0; i < n_edges; ++i) A.edges[i] = edges[i];
-    KP& P = A.kp;
-    hipStream_t st = stream_of(h, hip_stream);
-    const bool host = hip_stream == nullptr;
-    if (host) {
-        const size_t bytes = Bz * 8 * (5 + 2 + 3 * ncm + 5 * nem + nu + ALIPMPC_AUDIT_COLS) +
-                             Bz * (1 + 4 + 4 + 4 + 4 * ALIPMPC_AUDIT_WHERE) + nsum * 8 + 13 * 256;
-        if (int rc = ensure_stage(h, bytes)) return rc;
-        Carver cv{(char*)h->stage};
-        double* dx = cv.take<double>(Bz * 5);
-        double* dg = cv.take<double>(Bz * 2);
-        double* dc = cv.take<double>(Bz * 3 * ncm);
-        double* de = cv.take<double>(Bz * 5 * nem);
-        double* du = cv.take<double>(Bz * nu);
-        double* dm = cv.take<double>(Bz * ALIPMPC_AUDIT_COLS);
-        int64_t* ds = cv.take<int64_t>(nsum);
-        int32_t* dnc = cv.take<int32_t>(Bz);
-        int32_t* dne = cv.take<int32_t>(Bz);
-        int32_t* dst = cv.take<int32_t>(Bz);
-        int32_t* dw = cv.take<int32_t>(Bz * ALIPMPC_AUDIT_WHERE);
-        int8_t* dl = cv.take<int8_t>(Bz);
-        auto h2d = [&](void* d, const void* s, size_t n) { return hipMemcpyAsync(d, s, n, hipMemcpyHostToDevice, st); };
-        HIPCHK(h, h2d(dx, x0, Bz * 5 * 8));
-        HIPCHK(h, h2d(dg, goal, Bz * 2 * 8));
-        HIPCHK(h, h2d(dl, leg, Bz));
-        if (ncm) HIPCHK(h, h2d(dc, cir, Bz * 3 * ncm * 8));
-        HIPCHK(h, h2d(dnc, nc, Bz * 4));
-        if (nem) {
-            HIPCHK(h, h2d(de, elp, Bz * 5 * nem * 8));
-            HIPCHK(h, h2d(dne, ne, Bz * 4));
-        }
-        HIPCHK(h, h2d(du, u, Bz * nu * 8));
-        if (status) HIPCHK(h, h2d(dst, status, Bz * 4));
-        if (summary) HIPCHK(h, h2d(ds, summary, nsum * 8));
-        P.x0 = dx; P.goal = dg; P.leg = dl; P.cir = dc; P.nc = dnc;
-        P.elp = nem ? de : nullptr; P.ne = nem ? dne : nullptr; P.u0 = du;
-        A.status = status ? dst : nullptr;
-        A.metrics = metrics ? dm : nullptr;
-        A.where = where ? dw : nullptr;
-        A.summary = summary ? (unsigned long long*)ds : nullptr;
-    } else {
-        P.x0 = x0; P.goal = goal; P.leg = leg; P.cir = cir; P.nc = nc;
-        P.elp = nem ? elp : nullptr; P.ne = nem ? ne : nullptr; P.u0 = u;
-        A.status = status; A.metrics = metrics; A.where = where; A.summary = (unsigned long long*)summary;
-    }
-    HIPCHK(h, launch_audit(N, A, st));
-    if (host) {
-        if (metrics) HIPCHK(h, hipMemcpyAsync(metrics, A.metrics, Bz * ALIPMPC_AUDIT_COLS * 8, hipMemcpyDeviceToHost, st));
-        if (where) HIPCHK(h, hipMemcpyAsync(where, A.where, Bz * ALIPMPC_AUDIT_WHERE * 4, hipMemcpyDeviceToHost, st));
-        if (summary) HIPCHK(h, hipMemcpyAsync(summary, A.summary, nsum * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipStreamSynchronize(st));
-    }
-    return ALIPMPC_OK;
-}
-
-int alipmpc_nominal_gait_batch(void* handle, int64_t B, double vx_max, const double* x, const int8_t* leg,
-                               const double* vel_des_in, double* vel_des, double* foot, void* hip_stream)
-{
-    Handle* h = (Handle*)handle;
-    if (!h) return ALIPMPC_EINVAL;
-    const alipmpc_cfg& cf = h->cfg;
-    if (cf.variant == ALIPMPC_VARIANT_DD) return fail(h, ALIPMPC_EUNSUPPORTED, "nominal gait: LIP variants only");
-    if (B < 0) return fail(h, ALIPMPC_EINVAL, "B < 0");
-    if (B == 0) return ALIPMPC_OK;
-    if (!x || !foot || (!leg && !vel_des_in)) return fail(h, ALIPMPC_EINVAL, "missing pointer");
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t Bz = (size_t)B;
-    NgP Q;
-    std::memset(&Q, 0, sizeof(Q));
-    Q.B = B;
-    {
-        const double b = std::sqrt(cf.g / cf.H), T = cf.dt, sh = std::sinh(b * T), ch = std::cosh(b * T);
-        const double sigma = b / std::tanh(T * b / 2);   // beta coth(beta T / 2)
-        Q.vdx = sigma * vx_max * T / 2;
-        Q.vdy0 = (b * sh) / (ch + 1);
-        Q.bsh = sh * b;
-        Q.ch = ch;
-        Q.ibv = 1.0 / (-sh * b);
-    }
-    hipStream_t st = stream_of(h, hip_stream);
-    const bool host = hip_stream == nullptr;
-    if (host) {
-        if (int rc = ensure_stage(h, Bz * 8 * (5 + 2 + 2 + 2) + Bz + 5 * 256)) return rc;   // 5 carves, 256 B aligned
-        Carver cv{(char*)h->stage};
-        double* dx = cv.take<double>(Bz * 5);
-        double* dvi = cv.take<double>(Bz * 2);
-        double* dvo = cv.take<double>(Bz * 2);
-        double* df = cv.take<double>(Bz * 2);
-        int8_t* dl = cv.take<int8_t>(Bz);
-        HIPCHK(h, hipMemcpyAsync(dx, x, Bz * 5 * 8, hipMemcpyHostToDevice, st));
-        if (vel_des_in) HIPCHK(h, hipMemcpyAsync(dvi, vel_des_in, Bz * 2 * 8, hipMemcpyHostToDevice, st));
-        if (leg) HIPCHK(h, hipMemcpyAsync(dl, leg, Bz, hipMemcpyHostToDevice, st));
-        Q.x = dx; Q.vin = vel_des_in ? dvi : nullptr; Q.leg = leg ? dl : nullptr;
-        Q.vout = vel_des ? dvo : nullptr; Q.foot = df;
-    } else {
-        Q.x = x; Q.vin = vel_des_in; Q.leg = leg; Q.vout = vel_des; Q.foot = foot;
-    }
-    hipLaunchKernelGGL(nominal_gait_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, Q);
-    HIPCHK(h, hipGetLastError());
-    if (host) {
-        if (vel_des) HIPCHK(h, hipMemcpyAsync(vel_des, Q.vout, Bz * 2 * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipMemcpyAsync(foot, Q.foot, Bz * 2 * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipStreamSynchronize(st));
-    }
-    return ALIPMPC_OK;
-}
-
-int alipmpc_scenes_batch(void* handle, int64_t B, uint64_t seed, int64_t first_index, int32_t n_cir, int32_t n_elp,
-                         int64_t fields, int32_t max_candidates, double* x0, double* goal, int8_t* leg, double* cir,
-                         int32_t* nc, double* elp, int32_t* ne, double* u0, void* hip_stream)
-{
-    Handle* h = (Handle*)handle;
-    if (!h) return ALIPMPC_EINVAL;
-    const alipmpc_cfg& cf = h->cfg;
-    if (cf.variant == ALIPMPC_VARIANT_DD) return fail(h, ALIPMPC_EUNSUPPORTED, "scenes: LIP variants only");
-    if (B < 0) return fail(h, ALIPMPC_EINVAL, "B < 0");
-    if (n_cir < 0 || n_cir > cf.nc_max) return fail(h, ALIPMPC_EINVAL, "scenes: n_cir outside [0, nc_max]");
-    if (n_elp < 0 || n_elp > cf.ne_max) return fail(h, ALIPMPC_EINVAL, "scenes: n_elp outside [0, ne_max]");
-    if (n_cir + n_elp > ALIPMPC_MAX_OBS) return fail(h, ALIPMPC_EINVAL, "scenes: n_cir + n_elp > ALIPMPC_MAX_OBS");
-    if (n_elp > 0 && n_cir - n_elp != 0 && n_cir - n_elp != 1)
-        return fail(h, ALIPMPC_EINVAL, "scenes: a mix field needs n_cir = ceil(tot / 2), n_elp = floor(tot / 2)");
-    if (fields < 0) return fail(h, ALIPMPC_EINVAL, "scenes: fields < 0");
-    if (max_candidates < 0 || max_candidates > SC_MAX_CAND)
-        return fail(h, ALIPMPC_EINVAL, "scenes: max_candidates outside [0, 2^18]");
-    const int64_t id_end = (int64_t)1 << 40;
-    if (first_index < 0 || first_index > id_end || B > id_end - first_index)
-        return fail(h, ALIPMPC_EINVAL, "scenes: global indices outside [0, 2^40)");
-    if (B == 0) return ALIPMPC_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t Bz = (size_t)B, ncm = (size_t)cf.nc_max, nem = (size_t)cf.ne_max, nu = (size_t)5 * h->N;
-    ScP S;
-    std::memset(&S, 0, sizeof(S));
-    S.B = B; S.first = first_index; S.fields = fields; S.seed = seed;
-    S.n_cir = n_cir; S.n_elp = n_elp; S.nc_max = cf.nc_max; S.ne_max = cf.ne_max; S.N = h->N;
-    S.max_cand = max_candidates ? max_candidates : SC_MAX_CAND;
-    hipStream_t st = stream_of(h, hip_stream);
-    const bool host = hip_stream == nullptr;
-    if (!nem) elp = nullptr, ne = nullptr;   // no ellipse slots: ignored
-    if (host) {
-        if (int rc = ensure_stage(h, Bz * 8 * (5 + 2 + 3 * ncm + 5 * nem + nu) + Bz * (1 + 4 + 4) + 8 * 256)) return rc;
-        Carver cv{(char*)h->stage};
-        S.x0 = x0 ? cv.take<double>(Bz * 5) : nullptr;
-        S.goal = goal ? cv.take<double>(Bz * 2) : nullptr;
-        S.cir = cir ? cv.take<double>(Bz * 3 * ncm) : nullptr;
-        S.elp = elp ? cv.take<double>(Bz * 5 * nem) : nullptr;
-        S.u0 = u0 ? cv.take<double>(Bz * nu) : nullptr;
-        S.nc = nc ? cv.take<int32_t>(Bz) : nullptr;
-        S.ne = ne ? cv.take<int32_t>(Bz) : nullptr;
-        S.leg = leg ? cv.take<int8_t>(Bz) : nullptr;
-    } else {
-        S.x0 = x0; S.goal = goal; S.leg = leg; S.cir = cir; S.nc = nc; S.elp = elp; S.ne = ne; S.u0 = u0;
-    }
-    // one wavefront per instance; a bounded grid strides over larger batches
-    const long long blocks = std::min<long long>((B + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 1ll << 20);
-    hipLaunchKernelGGL(scenes_kernel, dim3((unsigned)blocks), dim3(WAVE * WAVES_PER_BLOCK), 0, st, S);
-    HIPCHK(h, hipGetLastError());
-    if (host) {
-        if (x0) HIPCHK(h, hipMemcpyAsync(x0, S.x0, Bz * 5 * 8, hipMemcpyDeviceToHost, st));
-        if (goal) HIPCHK(h, hipMemcpyAsync(goal, S.goal, Bz * 2 * 8, hipMemcpyDeviceToHost, st));
-        if (cir && ncm) HIPCHK(h, hipMemcpyAsync(cir, S.cir, Bz * 3 * ncm * 8, hipMemcpyDeviceToHost, st));
-        if (elp) HIPCHK(h, hipMemcpyAsync(elp, S.elp, Bz * 5 * nem * 8, hipMemcpyDeviceToHost, st));
-        if (u0) HIPCHK(h, hipMemcpyAsync(u0, S.u0, Bz * nu * 8, hipMemcpyDeviceToHost, st));
-        if (nc) HIPCHK(h, hipMemcpyAsync(nc, S.nc, Bz * 4, hipMemcpyDeviceToHost, st));
-        if (ne) HIPCHK(h, hipMemcpyAsync(ne, S.ne, Bz * 4, hipMemcpyDeviceToHost, st));
-        if (leg) HIPCHK(h, hipMemcpyAsync(leg, S.leg, Bz, hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipStreamSynchronize(st));
-    }
-    return ALIPMPC_OK;
-}
-
-#ifdef ALIP_STAMPS
-int alipmpc_dbg_stamps(unsigned long long* out, int reset)
-{
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(alip::g_stamps), sizeof(unsigned long long) * alip::NSTAMP) != hipSuccess)
-        return -1;
-    if (reset) {
-        unsigned long long z[alip::NSTAMP] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(alip::g_stamps), z, sizeof(z)) != hipSuccess) return -1;
-    }
-    return alip::NSTAMP;
-}
-#endif
-
-#ifdef ALIP_WSTAMP
-// diagnostic: copy the first `slots` per-instance records (8 values each) of the wave program and reset the base
-int alipmpc_dbg_wstamps(unsigned long long* out, long long slots)
-{
-    if (slots > alip::WSTAMP_CAP) slots = alip::WSTAMP_CAP;
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(alip::g_wstamp), sizeof(unsigned long long) * 8 * (size_t)slots) != hipSuccess)
-        return -1;
-    const long long z = 0;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(alip::g_wstamp_base), &z, sizeof(z)) != hipSuccess) return -1;
-    void* p = nullptr;
-    if (hipGetSymbolAddress(&p, HIP_SYMBOL(alip::g_wstamp)) != hipSuccess ||
-        hipMemset(p, 0, sizeof(unsigned long long) * 8 * (size_t)alip::WSTAMP_CAP) != hipSuccess)
-        return -1;
-    return (int)slots;
-}
-#endif
-
-// test hook (not part of the ABI): wave_helpers_kernel on host arrays — in (nsets x 128), sys (nsys x 90),
-// out (nsets x alip::WH_SET), gj_out (nsys x 20); returns alip::WH_SET, or -1 on a HIP error
-int alipmpc_dbg_wave_helpers(const double* in, int nsets, const double* sys, int nsys, double* out, double* gj_out)
-{
-    if (nsets < 0 || nsys < 0 || nsets > 4096 || nsys > 4096) return -1;
-    const size_t zi = sizeof(double) * 2 * alip::WAVE * (size_t)nsets, zs = sizeof(double) * 90 * (size_t)nsys;
-    const size_t zo = sizeof(double) * alip::WH_SET * (size_t)nsets, zg = sizeof(double) * 20 * (size_t)nsys;
-    double* d = nullptr;
-    if (hipMalloc((void**)&d, zi + zs + zo + zg + 8) != hipSuccess) return -1;
-    double *di = d, *ds = di + 2 * alip::WAVE * (size_t)nsets, *dout = ds + 90 * (size_t)nsys,
-           *dg = dout + alip::WH_SET * (size_t)nsets;
-    bool ok = (zi == 0 || hipMemcpy(di, in, zi, hipMemcpyHostToDevice) == hipSuccess) &&
-              (zs == 0 || hipMemcpy(ds, sys, zs, hipMemcpyHostToDevice) == hipSuccess);
-    if (ok) {
-        hipLaunchKernelGGL(alip::wave_helpers_kernel, dim3(1), dim3(alip::WAVE), 0, 0, di, nsets, ds, nsys, dout, dg);
-        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
-             (zo == 0 || hipMemcpy(out, dout, zo, hipMemcpyDeviceToHost) == hipSuccess) &&
-             (zg == 0 || hipMemcpy(gj_out, dg, zg, hipMemcpyDeviceToHost) == hipSuccess);
-    }
-    hipFree(d);
-    return ok ? alip::WH_SET : -1;
-}
-
-const char* alipmpc_build_id(void)
-{
-#ifdef ALIP_BUILD_ID
-    return ALIP_BUILD_ID;
-#else
-    return "unknown";
-#endif
-}
-
-double alipmpc_last_kernel_ms(void* handle)
-{
-    Handle* h = (Handle*)handle;
-    if (!h || !h->timed) return 0.0;
-    if (h->evlast < 0) return 0.0;
-    hipEvent_t e0 = h->ev[h->evlast][0], e1 = h->ev[h->evlast][1];
-    if (hipEventSynchronize(e1) != hipSuccess) return 0.0;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, e0, e1) != hipSuccess) return 0.0;
-    return (double)ms;
-}
-
-const char* alipmpc_last_error(void* handle)
-{
-    Handle* h = (Handle*)handle;
-    return h ? h->err.c_str() : "null handle";
-}
-
-int alipmpc_solve_slots(void* handle, int64_t* slots)
-{
-    Handle* h = (Handle*)handle;
-    if (!h || !slots) return fail(h, ALIPMPC_EINVAL, "null argument");
-    HIPCHK(h, hipSetDevice(h->device));
-    unsigned res = 0;
-    KP P = make_kp(h, 1, true);
-    HIPCHK(h, launch(h, true, P, h->own, &res));
-    if (h->lane_nct >= 0)
-        *slots = (int64_t)res * (h->cfg.precision == ALIPMPC_PREC_FP32 ? lane::lanes_of<float>() : lane::lanes_of<double>());
-    else
-        *slots = (int64_t)res * WAVES_PER_BLOCK;
-    return ALIPMPC_OK;
-}
-
-int alipmpc_lane_handoffs(void* handle, void* hip_stream, int64_t* count)
-{
-    Handle* h = (Handle*)handle;
-    if (!h || !count) return fail(h, ALIPMPC_EINVAL, "null argument");
-    *count = 0;
-    hipStream_t st = stream_of(h, hip_stream);
-    void* p = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(h->split_mtx);
-        auto it = h->redo.find(st);
-        if (it != h->redo.end()) p = it->second.p;
-    }
-    if (!p) return ALIPMPC_OK;
-    uint32_t c = 0;
-    if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(&c, p, sizeof(c), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(h, ALIPMPC_EHIP, "alipmpc_lane_handoffs: reading the hand-off count");
-    *count = c;
-    return ALIPMPC_OK;
-}
-
-int alipmpc_solve_launches(void* handle, int64_t B, int32_t* launches, int32_t* team)
-{
-    Handle* h = (Handle*)handle;
-    if (!h || !launches || !team) return fail(h, ALIPMPC_EINVAL, "null argument");
-    int64_t slots = 0;
-    if (int rc = alipmpc_solve_slots(handle, &slots)) return rc;
-    // launch_solve's conditions for the split form (no order / active mask on the batch API)
-    const bool split = split_form(h, B, h->split_it, h->split_tr, slots);
-    *launches = split ? 2 : 1;
-    *team = split && h->split_tr > 0 && h->cfg.precision != ALIPMPC_PREC_FP32 ? TEAM_WAVES : 1;
-    return ALIPMPC_OK;
-}
-
-const char* alipmpc_solve_program(void* handle)
-{
-    Handle* h = (Handle*)handle;
-    if (!h) return "";
-    static thread_local char buf[96];
-    const alipmpc_cfg& c = h->cfg;
-    const char* r = c.precision == ALIPMPC_PREC_FP32 ? "float" : "double";
-    if (c.variant == ALIPMPC_VARIANT_DD) {
-        const int rpl = h->mo4 / WAVE;
-        std::snprintf(buf, sizeof(buf), "dd_solve_kernel<%d,%d>", h->N, rpl);
-    } else if (h->lane_nct == LANE_FORM5) {
-        std::snprintf(buf, sizeof(buf), "lane_kernel<%d,5,true,Form<%s>>", h->N, r);
-    } else if (h->lane_nct >= 0) {
-        std::snprintf(buf, sizeof(buf), "lane_kernel<%d,%d,%s,%s>", h->N, h->lane_nct,
-                      c.variant == ALIPMPC_VARIANT_MODI ? "true" : "false", r);
-    } else {
-        std::snprintf(buf, sizeof(buf), "solve_kernel<%d,%d,%s>", h->N, h->mo4 / 4, r);
-    }
-    return buf;
-}
-
-void alipmpc_destroy(void* handle)
-{
-    Handle* h = (Handle*)handle;
-    if (!h) return;
-    hipSetDevice(h->device);
-    if (h->own) hipStreamSynchronize(h->own);
-    for (double* d : {h->dGp, h->dEp, h->dGu, h->dEu, h->dau})
-        if (d) (void)hipFree(d);
-    if (h->dq) hipFree(h->dq);
-    if (h->dlk) hipFree(h->dlk);
-    if (h->dlkf) hipFree(h->dlkf);
-    if (h->stage) hipFree(h->stage);
-    if (h->rstage) hipFree(h->rstage);
-    for (auto& kv : h->split)
-        if (kv.second.p) hipFree(kv.second.p);
-    for (auto& kv : h->redo)
-        if (kv.second.p) hipFree(kv.second.p);
-    for (auto& pr : h->ev)
-        for (hipEvent_t e : pr)
-            if (e) hipEventDestroy(e);
-    if (h->own) hipStreamDestroy(h->own);
-    for (int g = 0; g < Handle::MAXG; ++g) {
-        if (h->gst[g]) hipStreamDestroy(h->gst[g]);
-        if (h->gev[g]) hipEventDestroy(h->gev[g]);
-    }
-    if (h->gev[Handle::MAXG]) hipEventDestroy(h->gev[Handle::MAXG]);
-    delete h;
-}
-
-}  // extern "C"
+#include "host_api.inc"  // constants, handle, argument staging, C ABI
 #endif  // ALIP_PART_HOST
