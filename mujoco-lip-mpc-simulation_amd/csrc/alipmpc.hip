@@ -765,8 +765,12 @@ __device__ __forceinline__ double row_eval(const KP& P, const RowInfo& ri, const
 // Computed in fp64 for either workspace type (the discrete select/detour decisions do not depend on
 // cfg.precision); results are stored into the workspace's type.
 // ------------------------------------------------------------------------------------------------
-// 1/sqrt(d) and 1/x to ~1 ulp: hardware estimate + two Newton steps (a few FMAs instead of the
-// ~15-instruction IEEE sqrt / div sequences on the Cholesky critical path)
+// 1/sqrt(d) and 1/x: hardware estimate + two Newton steps (a few FMAs instead of the
+// ~15-instruction IEEE sqrt / div sequences on the Cholesky critical path).  Measured on the MI355X against a 200-bit
+// reference (tests/test_fastmath_gpu.py, profiles/fastmath/ulp.txt): rcp_nr 0.50 ulp over 2^+-960 (its last step is
+// in residual form, y + y e), rsqrt_nr 1.62 ulp (its steps are products y (1.5 - h y y): the factor next to 1 is
+// rounded to the result's precision before the product is).  rcp_nr(+-0) and rcp_nr(+-inf) are NaN (inf * 0 in the
+// step), not inf / 0: every caller tests its argument first.  rsqrt_nr(d < 0) is NaN.
 // binary exponent of a normal nonzero value (the trial count of a line search from a = ap 2^-j)
 __device__ __forceinline__ int fexp2(double x) { return __builtin_amdgcn_frexp_exp(x); }
 __device__ __forceinline__ int fexp2(float x) { return __builtin_amdgcn_frexp_expf(x); }
@@ -787,7 +791,8 @@ __device__ __forceinline__ double rcp_nr(double x)
     e = fma(-x, y, 1.0);
     return fma(y, e, y);
 }
-// fp32: the hardware estimates are ~1 ulp already; one Newton step makes them correctly rounded-ish
+// fp32: the hardware estimates are ~1 ulp already; one Newton step.  Measured over 2^+-100: rcp_nr 0.50 ulp (correctly
+// rounded on every argument of the test), rsqrt_nr 1.52 ulp (the product form, as above) — chol_rows is its only user
 __device__ __forceinline__ float rsqrt_nr(float d)
 {
     float y = __builtin_amdgcn_rsqf(d);
@@ -5455,6 +5460,86 @@ __global__ __launch_bounds__(WAVE) void wave_helpers_kernel(const double* in, in
             o[n] = ok_a ? 1.0 : 0.0;
             o[2 * n + 1] = ok_c ? 1.0 : 0.0;
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// test hook (alipmpc_dbg_fastmath, tests/test_fastmath_gpu.py): one numeric primitive per launch, one lane per
+// element, called as the kernels call it — no arithmetic around the call, so nothing contracts into it.  The fp32
+// ops cast the fp64 inputs down and widen the result (both exact or one rounding the test repeats).
+//    0 rcp_nr(a)   1 rsqrt_nr(a)   2 rcp_div(a, b)   3 div100(a)       4..7 the same in fp32
+//    8 lsincos(a) -> out0 = sin, out1 = cos          9 lsincos_sel
+//   10 latan(a)   11 latan_br(a)  12 latan2(a, b)   13 latan2_br(a, b)  14 llog(a)
+// ------------------------------------------------------------------------------------------------
+constexpr int FM_OPS = 15, FM_BLOCK = 256;
+template <int OP>
+__global__ __launch_bounds__(FM_BLOCK) void fastmath_kernel(const double* a, const double* b, long long n, double* out0,
+                                                            double* out1)
+{
+    const long long i = (long long)blockIdx.x * FM_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    if constexpr (OP == 0) out0[i] = rcp_nr(a[i]);
+    else if constexpr (OP == 1) out0[i] = rsqrt_nr(a[i]);
+    else if constexpr (OP == 2) out0[i] = rcp_div(a[i], b[i]);
+    else if constexpr (OP == 3) out0[i] = div100(a[i]);
+    else if constexpr (OP == 4) out0[i] = (double)rcp_nr((float)a[i]);
+    else if constexpr (OP == 5) out0[i] = (double)rsqrt_nr((float)a[i]);
+    else if constexpr (OP == 6) out0[i] = (double)rcp_div((float)a[i], (float)b[i]);
+    else if constexpr (OP == 7) out0[i] = (double)div100((float)a[i]);
+    else if constexpr (OP == 8 || OP == 9) {
+        double s, c;
+        if constexpr (OP == 8) lsincos(a[i], &s, &c);
+        else lsincos_sel(a[i], &s, &c);
+        out0[i] = s;
+        out1[i] = c;
+    } else if constexpr (OP == 10) out0[i] = latan(a[i]);
+    else if constexpr (OP == 11) out0[i] = latan_br(a[i]);
+    else if constexpr (OP == 12) out0[i] = latan2(a[i], b[i]);
+    else if constexpr (OP == 13) out0[i] = latan2_br(a[i], b[i]);
+    else out0[i] = llog(a[i]);
+}
+
+// ------------------------------------------------------------------------------------------------
+// test hook (alipmpc_dbg_kkt_solves, tests/test_kkt_solves_gpu.py): the KKT solvers on their own, one wave (one
+// block) per system, rows [K | rhs] of n x (n + 1) doubles cast to R, filled as solve_one fills them.
+//   FORM 0 / 1  gj_regs<n, R, false / true>: x[n s + i] = x_i
+//   FORM 2      gj_lds<n, n + 1, R> on an LDS copy (the ALIP_GJ_REGS=0 path): the same
+//   FORM 3      chol_rows<n, R>: x[n (n + 1) s + (n + 1) i + j] = L[i][j] (j <= i, 0 above), column n = idg[i]
+// ok[s] = the verdict; x of a system with ok = 0 is whatever the solver left.
+// ------------------------------------------------------------------------------------------------
+template <int FORM, int n, class R>
+__global__ __launch_bounds__(WAVE) void kkt_solves_kernel(const double* sys, double* x, int* ok)
+{
+    const int lane = lane_id();
+    const double* s = sys + (size_t)n * (n + 1) * blockIdx.x;
+    if constexpr (FORM == 3) {
+        R a[n], myidg = R(1.0);
+#pragma unroll
+        for (int j = 0; j < n; ++j) a[j] = lane < n ? (R)s[(n + 1) * lane + j] : (lane == j ? R(1.0) : R(0.0));
+        const bool good = chol_rows<n>(a, myidg, lane);
+        double* o = x + (size_t)n * (n + 1) * blockIdx.x;
+        if (lane < n) {
+#pragma unroll
+            for (int j = 0; j < n; ++j) o[(n + 1) * lane + j] = j <= lane ? (double)a[j] : 0.0;
+            o[(n + 1) * lane + n] = (double)myidg;
+        }
+        if (lane == 0) ok[blockIdx.x] = good ? 1 : 0;
+    } else if constexpr (FORM == 2) {
+        constexpr int LD = n + 1;
+        __shared__ R M[LD * LD];   // (row n holds the padding element M[n][n] only)
+        for (int e = lane; e < LD * LD; e += WAVE) M[e] = e < n * LD ? (R)s[e] : R(0.0);
+        wave_sync();
+        const bool good = gj_lds<n, LD>(M, lane);
+        wave_sync();
+        if (lane < n) x[(size_t)n * blockIdx.x + lane] = (double)M[lane * LD + n];
+        if (lane == 0) ok[blockIdx.x] = good ? 1 : 0;
+    } else {
+        R a[n + 1];
+#pragma unroll
+        for (int j = 0; j <= n; ++j) a[j] = lane < n ? (R)s[(n + 1) * lane + j] : R(0.0);
+        const bool good = gj_regs<n, R, FORM == 1>(a, lane);
+        if (lane < n) x[(size_t)n * blockIdx.x + lane] = (double)a[n];
+        if (lane == 0) ok[blockIdx.x] = good ? 1 : 0;
     }
 }
 #endif

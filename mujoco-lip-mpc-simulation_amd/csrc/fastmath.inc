@@ -1,9 +1,33 @@
-// fastmath.inc — compact fp64 sincos / atan / atan2 / log (~1 ulp) for the interior-point kernels.
+// fastmath.inc — compact fp64 sincos / atan / atan2 / log for the interior-point kernels.
 // Included by alipmpc.hip inside namespace alip, after rcp_nr.
-// ---- compact fp64 transcendentals (~1 ulp; fdlibm's published algorithms and minimax
-// coefficients, written out here): the ocml versions are 3-5x larger and every copy in the hot loop costs
-// instruction issue on every pass.  fp32 uses the ocml single-precision functions.
-__device__ __forceinline__ double rcp_div(double y, double x)   // y / x to ~1 ulp
+// ---- compact fp64 transcendentals (fdlibm's published algorithms and minimax coefficients, written out here): the
+// ocml versions are 3-5x larger and every copy in the hot loop costs instruction issue on every pass.  fp32 uses the
+// ocml single-precision functions.
+//
+// Accuracy, in ulp of the correctly rounded result, measured on the MI355X against a 200-bit reference
+// (tests/test_fastmath_gpu.py, profiles/fastmath/ulp.txt; in brackets the bar the test holds), and the domain each
+// function is correct on.  Outside it the values below are what the code returns, not libm's; nothing in the solver
+// reaches them (angles are headings, quotients come from coordinate differences of metre-sized numbers).
+//   rcp_div(y, x)   0.50 [1.5] (fp32 0.50 [0.5]).  1 / x and y / x within the normal range.  Where 1 / x or the
+//                   quotient overflows, x = +-0 or x = +-inf: NaN (rcp_nr, or inf * 0 in the correction).
+//   div100(x)       0.48 [1.5] (fp32 0.48 [0.5]).  Every x whose x / 100 is normal.
+//   lsincos(x)      sin 1.30, cos 1.37 [2.0] away from the multiples of pi/2.  The two-constant Cody-Waite reduction
+//                   leaves an absolute error of |k| C, k = rint(x 2/pi), C = |pi/2 - hi - lo| = 1.4973849e-33, so
+//                   the bound is |err| <= 2.0 ulp + |k| C: at the double nearest a multiple of pi/2 that is 451 ulp
+//                   of the tiny result for |k| <= 64 and 548 ulp among 2000 random |k| <= 6.4e5 (0.996 of the
+//                   bound both times) — below 1e-27 in absolute terms.  Domain |x| < 1e6 (denormals and +-0
+//                   included).  lsincos(-0.0) returns +0 for the sine (k = -0, and (+0) + (-0) = +0 in the
+//                   reduction).  |x| >= 1e6: |k| C keeps growing, and from |k| >= 2^31 the quadrant (int)k is wrong.
+//                   +-inf, NaN: NaN.
+//   latan(x)        0.78 [1.5].  x >= 0, +inf included (pi/2); x = NaN: NaN; x < 0 is not handled.
+//   latan2(y, x)    1.30 [2.0].  Finite arguments whose quotient |y / x| and 1 / |x| are within the normal range, and
+//                   the axes: (+-0, x > 0) -> +-0, (+-0, x < 0) -> +-pi, (y != 0, +-0) -> +-pi/2, (+-0, +0) -> +-0.
+//                   latan2(+-0, -0.0) is +-0 where libm has +-pi.  Where 1 / |x| or the quotient overflows (latan2(1,
+//                   1e-310), latan2(1e200, 1e-200)) or an argument is infinite: NaN (rcp_div), where libm has +-pi/2,
+//                   +-0, +-pi or a multiple of pi/4.
+//   llog(x)         0.66 [1.5].  x > 0 finite, denormals included; +-0 -> -inf, x < 0 or NaN -> NaN, +inf -> +inf.
+// lsincos = lsincos_sel, latan = latan_br and latan2 = latan2_br bit for bit on every argument of those sets.
+__device__ __forceinline__ double rcp_div(double y, double x)   // y / x (0.50 ulp measured, see above)
 {
     const double r = rcp_nr(x);
     const double q = y * r;
@@ -15,7 +39,7 @@ __device__ __forceinline__ float rcp_div(float y, float x)
     const float q = y * r;
     return fmaf(r, fmaf(-q, x, y), q);
 }
-// x / 100 to ~1 ulp (the scaling of IPOPT's s_max = 100): the product with 0.01 and its residual correction
+// x / 100 (0.48 ulp measured; the scaling of IPOPT's s_max = 100): the product with 0.01 and its residual correction
 __device__ __forceinline__ double div100(double x)
 {
     const double q = x * 0.01;

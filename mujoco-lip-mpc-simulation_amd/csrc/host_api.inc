@@ -1660,6 +1660,98 @@ int alipmpc_dbg_wave_helpers(const double* in, int nsets, const double* sys, int
     return ok ? alip::WH_SET : -1;
 }
 
+// test hook (not part of the ABI): fastmath_kernel<op> on host arrays of n elements (b: the second argument of
+// rcp_div / latan2, otherwise unused and may be null; out1: the cosine of lsincos, otherwise untouched and may be
+// null); returns 0, or -1 on a bad argument or a HIP error
+extern "C++" {
+template <int OP>
+static void dbg_fastmath_launch(int op, const double* a, const double* b, long long n, double* o0, double* o1)
+{
+    if constexpr (OP < alip::FM_OPS) {
+        if (op == OP)
+            hipLaunchKernelGGL(alip::fastmath_kernel<OP>, dim3((unsigned)((n + alip::FM_BLOCK - 1) / alip::FM_BLOCK)),
+                               dim3(alip::FM_BLOCK), 0, 0, a, b, n, o0, o1);
+        else
+            dbg_fastmath_launch<OP + 1>(op, a, b, n, o0, o1);
+    }
+}
+}  // extern "C++"
+int alipmpc_dbg_fastmath(int op, const double* a, const double* b, int64_t n, double* out0, double* out1)
+{
+    if (op < 0 || op >= alip::FM_OPS || n < 0 || n > (int64_t(1) << 22) || !a || !out0) return -1;
+    const bool two_in = op == 2 || op == 6 || op == 12 || op == 13, two_out = op == 8 || op == 9;
+    if ((two_in && !b) || (two_out && !out1)) return -1;
+    if (n == 0) return 0;
+    const size_t z = sizeof(double) * (size_t)n;
+    double* d = nullptr;
+    if (hipMalloc((void**)&d, 4 * z) != hipSuccess) return -1;
+    double *da = d, *db = d + n, *d0 = d + 2 * n, *d1 = d + 3 * n;
+    bool ok = hipMemcpy(da, a, z, hipMemcpyHostToDevice) == hipSuccess &&
+              (!two_in || hipMemcpy(db, b, z, hipMemcpyHostToDevice) == hipSuccess);
+    if (ok) {
+        dbg_fastmath_launch<0>(op, da, db, (long long)n, d0, d1);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+             hipMemcpy(out0, d0, z, hipMemcpyDeviceToHost) == hipSuccess &&
+             (!two_out || hipMemcpy(out1, d1, z, hipMemcpyDeviceToHost) == hipSuccess);
+    }
+    hipFree(d);
+    return ok ? 0 : -1;
+}
+
+// test hook (not part of the ABI): kkt_solves_kernel on host arrays, one wave per system.  form 0 / 1: gj_regs with
+// readlane / row broadcasts, 2: gj_lds (n = 3, 6, 9, 12, 15; x is nsys x n), 3: chol_rows (n = 18; x is
+// nsys x n x (n + 1), L and the idg column); sys is nsys x n x (n + 1) rows [K | rhs]; ok gets the verdicts.
+// Returns 0, or -1 on a shape the hook does not hold or a HIP error
+extern "C++" {
+template <int FORM, int N, class R>
+static void dbg_kkt_launch(const double* s, int nsys, double* x, int* ok)
+{
+    hipLaunchKernelGGL((alip::kkt_solves_kernel<FORM, N, R>), dim3(nsys), dim3(alip::WAVE), 0, 0, s, x, ok);
+}
+template <int FORM, class R>
+static bool dbg_kkt_pick(int n, const double* s, int nsys, double* x, int* ok)
+{
+    switch (n) {
+    case 3: dbg_kkt_launch<FORM, 3, R>(s, nsys, x, ok); return true;
+    case 6: dbg_kkt_launch<FORM, 6, R>(s, nsys, x, ok); return true;
+    case 9: dbg_kkt_launch<FORM, 9, R>(s, nsys, x, ok); return true;
+    case 12: dbg_kkt_launch<FORM, 12, R>(s, nsys, x, ok); return true;
+    case 15: dbg_kkt_launch<FORM, 15, R>(s, nsys, x, ok); return true;
+    default: return false;
+    }
+}
+}  // extern "C++"
+int alipmpc_dbg_kkt_solves(int form, int n, int fp32, const double* sys, int nsys, double* x, int32_t* ok)
+{
+    if (form < 0 || form > 3 || nsys < 0 || nsys > 65536 || n < 1 || n > 18 || !sys || !x || !ok) return -1;
+    if (form == 3 ? n != 18 : (n % 3 != 0 || n > 15)) return -1;
+    if (nsys == 0) return 0;
+    const size_t ns = (size_t)nsys * n * (n + 1), nx = form == 3 ? ns : (size_t)nsys * n;
+    double* d = nullptr;
+    if (hipMalloc((void**)&d, sizeof(double) * (ns + nx) + sizeof(int) * (size_t)nsys) != hipSuccess) return -1;
+    double *ds = d, *dx = d + ns;
+    int* dok = (int*)(dx + nx);
+    bool ok_ = hipMemcpy(ds, sys, sizeof(double) * ns, hipMemcpyHostToDevice) == hipSuccess &&
+               hipMemset(dx, 0, sizeof(double) * nx + sizeof(int) * (size_t)nsys) == hipSuccess;
+    if (ok_) {
+        if (form == 3) {
+            if (fp32) dbg_kkt_launch<3, 18, float>(ds, nsys, dx, dok);
+            else dbg_kkt_launch<3, 18, double>(ds, nsys, dx, dok);
+        } else if (form == 2) {
+            ok_ = fp32 ? dbg_kkt_pick<2, float>(n, ds, nsys, dx, dok) : dbg_kkt_pick<2, double>(n, ds, nsys, dx, dok);
+        } else if (form == 1) {
+            ok_ = fp32 ? dbg_kkt_pick<1, float>(n, ds, nsys, dx, dok) : dbg_kkt_pick<1, double>(n, ds, nsys, dx, dok);
+        } else {
+            ok_ = fp32 ? dbg_kkt_pick<0, float>(n, ds, nsys, dx, dok) : dbg_kkt_pick<0, double>(n, ds, nsys, dx, dok);
+        }
+        ok_ = ok_ && hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+              hipMemcpy(x, dx, sizeof(double) * nx, hipMemcpyDeviceToHost) == hipSuccess &&
+              hipMemcpy(ok, dok, sizeof(int) * (size_t)nsys, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    hipFree(d);
+    return ok_ ? 0 : -1;
+}
+
 const char* alipmpc_build_id(void)
 {
 #ifdef ALIP_BUILD_ID
