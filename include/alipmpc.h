@@ -318,6 +318,42 @@ int alipmpc_closed_loop_dataset_batch(void* handle, int64_t B, int32_t S, int32_
                                       int64_t first_index, double safe_dis, int64_t max_rows, double* X, double* y_mpc,
                                       double* y_act, int32_t* row_status, int64_t* row_start, void* hip_stream);
 
+/*
+ * Closed loop that solves on scheduled ticks only: the reference's hybrid driver (main_sim_mpc_alip.py:71-130, 20 ticks
+ * per step and ONE solve per step at tick s_mpc = 15, Logger.gen_nex_foot_input; every other tick Logger.cal_foot_input,
+ * data_procs/logger.py:380-418) on the plant, inputs, outputs, pointer modes, episode groups, kick stream and stop
+ * rule of alipmpc_closed_loop_batch.  Bit i of mpc_mask set: tick i of every step solves.  f_cyc outside 1..64 or a
+ * mask bit at or above f_cyc: ALIPMPC_EINVAL; DD: ALIPMPC_EUNSUPPORTED.
+ *   A solve tick is alipmpc_closed_loop_batch's tick (the all-ones mask gives its outputs bit for bit, with the same
+ *   launches when plan_traj is NULL); plan_traj[b, s, i] also receives the solve's u.
+ *   A nominal tick (logger.py:380-410, main_sim_mpc_alip.py:96-105, 121-124): set_stf_head at i == 0 as ever; x_nex =
+ *   get_next_states(plant, [stance foot, hd_input_pr], rest_t); the foothold target f = cal_foot_with_veldes(x_nex,
+ *   v_des_map) = B_vel^-1 (v_des_map - (A x_nex)[2:4]), the one-step deadbeat ALIP law that realises the plan's
+ *   desired touchdown velocity; the command is action_traj's with f in place of p_list[0][0:2]; the plant moves
+ *   T / f_cyc and takes the kick.  nex_turn, mpc_hds_list, the plan, v_des_map and the close flag stay as the last solve
+ *   left them.  status_traj = ALIPMPC_TICK_NOMINAL, iters_traj = 0, the plan_traj row is NaN.
+ *   Touchdown on a nominal last tick: stance foot <- f, foot_traj[b, s] = [f, nex_turn as it stands], leg_ind <-
+ *   -leg_ind, v_des_map <- plan row 1 [2:4] (row 0 at N = 1; alip_des_vel(0.6, the new leg_ind) before the first
+ *   solve), then the stop test.
+ * Deviation: only solves set the close flag, and an episode stops at a touchdown after a solve reported
+ * close_2_goal — alipmpc_closed_loop_batch's rule, so that the all-ones mask IS that loop; the reference's hybrid
+ * driver breaks at the tick itself (main_sim_mpc_alip.py:129).
+ * plan_traj: B x S x f_cyc x 5N, may be NULL (NaN after the stop).  Mask 0 is the nominal gait baseline: no solve.
+ * Launches: a maximal run of consecutive nominal ticks — it may cross step boundaries — is ONE launch that keeps the
+ * episode's state in registers (mask 1 << 15 at f_cyc 20: two small launches and one solve per step; mask 0: one
+ * launch per loop); the flow constants of every tick travel in the launch's arguments, so device-pointer calls stay
+ * copy-free and allocation-free.  ALIPMPC_CL_FUSE=0 (development, read per call) launches the same kernel once per
+ * nominal tick instead: the same bits.
+ */
+#define ALIPMPC_TICK_NOMINAL (-20)   /* status_traj: the tick ran the nominal ALIP law, no solve */
+int alipmpc_closed_loop_schedule_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc, uint64_t mpc_mask,
+                                       double kick, uint64_t seed,
+                                       const double* x0, const double* foot0, const double* goal, const int8_t* leg,
+                                       const double* cir, const int32_t* nc, const double* elp, const int32_t* ne,
+                                       double* foot_traj, double* x_traj, double* hd_traj, int32_t* status_traj,
+                                       int32_t* iters_traj, int32_t* steps_to_goal, double* action_traj,
+                                       double* plan_traj, void* hip_stream);
+
 /* Nominal gait of a batch (replaces MPCCBF.alip_des_vel / cal_foot_with_veldes, MPC_LIP_modi.py:181-194, used by
  * the driver at main_sim_mpc.py:54 and the ALIP-only loggers):
  *   vel_des = alip_des_vel(vx_max, leg_ind) = [sigma vx_max T / 2, 0.5 (-0.5 leg_ind step_gap) beta sinh(beta T) /

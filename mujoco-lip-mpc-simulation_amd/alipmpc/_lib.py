@@ -24,6 +24,7 @@ STATUS_NAMES = {0: "Solve_Succeeded", 1: "Solved_To_Acceptable_Level", 2: "Infea
                 -13: "Invalid_Number_Detected (cfg.goal_singular = GOAL_SINGULAR_ABORT)",
                 -10: "Rollout_Done (goal reached earlier, not solved)"}
 ROLLOUT_DONE = -10
+TICK_NOMINAL = -20   # closed_loop_schedule: the tick ran the nominal ALIP law, no solve (ALIPMPC_TICK_NOMINAL)
 
 _ERRORS = {-1: "EINVAL", -2: "ENODEV (no visible gfx950 device)", -3: "EHIP", -4: "EUNSUPPORTED"}
 
@@ -44,7 +45,7 @@ class Cfg(ctypes.Structure):
 
 EXPORTS = ("alipmpc_default_cfg", "alipmpc_rows_per_step", "alipmpc_num_vars", "alipmpc_create",
            "alipmpc_solve_batch", "alipmpc_eval_batch", "alipmpc_rollout_batch", "alipmpc_closed_loop_batch",
-           "alipmpc_closed_loop_dataset_batch", "alipmpc_trace_len",
+           "alipmpc_closed_loop_dataset_batch", "alipmpc_closed_loop_schedule_batch", "alipmpc_trace_len",
            "alipmpc_trace_batch", "alipmpc_nominal_gait_batch", "alipmpc_solve_slots", "alipmpc_solve_launches", "alipmpc_lane_handoffs", "alipmpc_solve_program", "alipmpc_last_kernel_ms",
            "alipmpc_build_id", "alipmpc_scenes_batch", "alipmpc_audit_summary_len", "alipmpc_audit_batch",
            "alipmpc_last_error", "alipmpc_destroy")
@@ -98,6 +99,10 @@ def load(build_if_missing=True):
                                                         ctypes.c_double, ctypes.c_uint64] + [P] * 15 + \
                                                        [ctypes.c_int64, ctypes.c_double, ctypes.c_int64] + [P] * 6
         L.alipmpc_closed_loop_dataset_batch.restype = ctypes.c_int
+    if hasattr(L, "alipmpc_closed_loop_schedule_batch"):   # (absent from older dev builds used for A/B timing)
+        L.alipmpc_closed_loop_schedule_batch.argtypes = [P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                         ctypes.c_uint64, ctypes.c_double, ctypes.c_uint64] + [P] * 17
+        L.alipmpc_closed_loop_schedule_batch.restype = ctypes.c_int
     L.alipmpc_trace_len.argtypes = [ctypes.POINTER(Cfg)]
     L.alipmpc_trace_len.restype = ctypes.c_int32
     L.alipmpc_trace_batch.argtypes = [P, ctypes.c_int64, P, P, P, P]
@@ -368,6 +373,44 @@ class Solver:
             _ptr(out.get("status")), _ptr(out.get("iters")), _ptr(out.get("steps_to_goal")), _ptr(out.get("action")),
             _stream_arg(st))
         self._check(rc, "alipmpc_closed_loop_batch")
+
+    def closed_loop_schedule(self, x0, foot0, goal, leg, cir, nc, elp=None, ne=None, steps=8, f_cyc=20,
+                             mpc_ticks=(15,), kick=0.0, seed=0, want_plans=False):
+        """Closed loop that solves on scheduled ticks only (alipmpc_closed_loop_schedule_batch): tick i of every step
+        solves the MPC if i is in mpc_ticks (an iterable of tick indices, or an int bit mask); every other tick takes
+        the nominal ALIP foothold cal_foot_with_veldes(x_nex, v_des) (status TICK_NOMINAL, 0 iterations).  The default
+        is the reference's hybrid driver (main_sim_mpc_alip.py: 20 ticks, one solve at tick 15).  Returns the dict of
+        closed_loop plus plan: (B, S, f_cyc, 5N) the u of every solved tick, NaN elsewhere (None unless want_plans)."""
+        from .schedule import mask_of
+        S, F = int(steps), int(f_cyc)
+        mask = mask_of(mpc_ticks)
+        B, x0, goal, leg, cir, nc, elp, ne = self._inputs(x0, goal, leg, cir, nc, elp, ne)
+        foot0 = np.ascontiguousarray(foot0, np.float64).reshape(B, 2)
+        out = dict(foot=np.zeros((B, S, 3)), x=np.zeros((B, S + 1, 5)), hd=np.zeros((B, S, 2)),
+                   status=np.zeros((B, S, F), np.int32), iters=np.zeros((B, S, F), np.int32),
+                   steps_to_goal=np.zeros(B, np.int32), action=np.zeros((B, S, F, 8)),
+                   plan=np.zeros((B, S, F, self.n)) if want_plans else None)
+        rc = self._L.alipmpc_closed_loop_schedule_batch(
+            self._h, B, S, F, mask, float(kick), int(seed), _ptr(x0), _ptr(foot0), _ptr(goal), _ptr(leg), _ptr(cir),
+            _ptr(nc), _ptr(elp), _ptr(ne), _ptr(out["foot"]), _ptr(out["x"]), _ptr(out["hd"]), _ptr(out["status"]),
+            _ptr(out["iters"]), _ptr(out["steps_to_goal"]), _ptr(out["action"]), _ptr(out["plan"]), None)
+        self._check(rc, "alipmpc_closed_loop_schedule_batch")
+        return out
+
+    def closed_loop_schedule_device(self, inp, out, steps, f_cyc=20, mpc_ticks=(15,), kick=0.0, seed=0, stream=None):
+        """Asynchronous scheduled closed loop on device tensors: inp / out as closed_loop_device, out also with plan
+        (B, S, f_cyc, 5N) if the plans are wanted."""
+        import torch
+        from .schedule import mask_of
+        st = stream if stream is not None else torch.cuda.current_stream()
+        B = inp["x0"].shape[0]
+        rc = self._L.alipmpc_closed_loop_schedule_batch(
+            self._h, B, int(steps), int(f_cyc), mask_of(mpc_ticks), float(kick), int(seed), _ptr(inp["x0"]),
+            _ptr(inp["foot0"]), _ptr(inp["goal"]), _ptr(inp["leg"]), _ptr(inp["cir"]), _ptr(inp["nc"]),
+            _ptr(inp.get("elp")), _ptr(inp.get("ne")), _ptr(out.get("foot")), _ptr(out.get("x")), _ptr(out.get("hd")),
+            _ptr(out.get("status")), _ptr(out.get("iters")), _ptr(out.get("steps_to_goal")), _ptr(out.get("action")),
+            _ptr(out.get("plan")), _stream_arg(st))
+        self._check(rc, "alipmpc_closed_loop_schedule_batch")
 
     def x_cols(self):
         """Columns of the dataset's X: 3 nc_max + 5 ne_max + 11 (include/alipmpc.h)."""

@@ -1,0 +1,286 @@
+"""The scheduled closed loop in numpy (alipmpc_closed_loop_schedule_batch, include/alipmpc.h): the hybrid driver of
+main_sim_mpc_alip.py:71-130 on an ALIP plant.  Tick i of a step solves the MPC when bit i of the mask is set
+(Logger.gen_nex_foot_input) and otherwise takes the foothold that realises the plan's desired touchdown velocity from
+the plant's projection (Logger.cal_foot_input, data_procs/logger.py:380-410: cal_foot_with_veldes(x_nex, v_des_map)).
+
+  run     drives the loop with any solver (a callable): the host restatement of the device loop
+  replay  recomputes every step of a device loop from the device's own touchdown state x[:, s] and its recorded plans,
+          so no drift crosses a step; also returns the solve inputs (x_nex, -leg_ind, u0) of every solved tick
+
+Built from the pieces of alipmpc.tsc (heading tube, command packing) and alipmpc.planner (ALIP matrices); every
+expression is written in the operation order of the device kernels (csrc/alipmpc.hip: cl_project_kernel,
+cl_update_kernel, cl_nominal_run_kernel, nominal_gait_kernel).
+"""
+import math
+
+import numpy as np
+
+from . import planner, tsc
+
+TICK_NOMINAL = -20     # ALIPMPC_TICK_NOMINAL
+ROLLOUT_DONE = -10     # ALIPMPC_ROLLOUT_DONE
+VARIANT_MODI, VARIANT_SIG_STEP = 0, 1
+MAX_F_CYC = 64
+
+_M64 = (1 << 64) - 1
+
+
+def mask_of(mpc_ticks, f_cyc=None):
+    """The schedule as a 64-bit mask: mpc_ticks is an int mask or an iterable of tick indices.  With f_cyc given,
+    ValueError for f_cyc outside 1..64 or a tick at or above f_cyc (the ABI's ALIPMPC_EINVAL cases); without, only
+    what 64 bits cannot hold is refused (the library checks the rest)."""
+    if isinstance(mpc_ticks, (int, np.integer)):
+        m = int(mpc_ticks)
+    else:
+        m = 0
+        for t in mpc_ticks:
+            t = int(t)
+            if not 0 <= t < MAX_F_CYC:
+                raise ValueError(f"tick {t} outside 0..{MAX_F_CYC - 1}")
+            m |= 1 << t
+    if not 0 <= m <= _M64:
+        raise ValueError("mask outside 64 bits")
+    if f_cyc is not None:
+        F = int(f_cyc)
+        if not 1 <= F <= MAX_F_CYC:
+            raise ValueError(f"f_cyc {F} outside 1..{MAX_F_CYC}")
+        if m >> F:
+            raise ValueError(f"mask {m:#x} has a tick at or above f_cyc = {F}")
+    return m
+
+
+def all_ones(f_cyc):
+    return (1 << int(f_cyc)) - 1
+
+
+def cl_uniform(seed, b, s, i, axis):
+    """splitmix64 uniform [0, 1) of (episode, step, tick, axis): the plant's velocity kick (cl_uniform of
+    csrc/alipmpc.hip, the same integer recipe)."""
+    key = ((((b * 1048576 + s) * 1024 + i) * 2 + axis) + 1) & _M64
+    z = (seed + 0x9E3779B97F4A7C15 * key) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    z = z ^ (z >> 31)
+    return (z >> 11) * (1.0 / 9007199254740992.0)
+
+
+def constants(cfg):
+    """The loop's constants of a cfg-like object (N, variant, dt, g, H): ALIP matrices of a whole step
+    (planner.alip_constants), alip_des_vel(0.6, .) and cal_foot_with_veldes's B_vel^-1."""
+    T = float(cfg.dt)
+    k = planner.alip_constants(T, float(cfg.g), float(cfg.H))
+    beta = k["beta"]
+    sh, ch = math.sinh(beta * T), math.cosh(beta * T)
+    return dict(N=int(cfg.N), variant=int(cfg.variant), T=T, beta=beta, A=k["A"], W=k["W"], M_A=k["M_A"],
+                M_B=k["M_B"], bsh=sh * beta, ch=ch, ibv=1.0 / (-sh * beta),
+                vdx=beta / math.tanh(T * beta / 2) * 0.6 * T / 2, vdy0=(beta * sh) / (ch + 1))
+
+
+def des_vel(k, leg):
+    """alip_des_vel(0.6, leg_ind) per episode (MPC_LIP_modi.py:181-186)."""
+    leg = np.asarray(leg, float)
+    return np.stack([np.full(leg.shape, k["vdx"]), 0.5 * (-0.5 * leg * 0.3) * k["vdy0"]], -1)
+
+
+def flow_consts(beta, t):
+    """cosh, sinh / beta, beta sinh of the ALIP flow over t."""
+    return math.cosh(beta * t), math.sinh(beta * t) / beta, math.sinh(beta * t) * beta
+
+
+def flow(x, fx, fy, hp, ch, shb, bsh, tt):
+    """get_next_states (MPC_LIP_modi.py:149-178): the state x (n, 5) moved around the stance foot (fx, fy) with the
+    heading advancing tt * hp."""
+    return np.stack([ch * x[:, 0] + shb * x[:, 2] + (1.0 - ch) * fx,
+                     ch * x[:, 1] + shb * x[:, 3] + (1.0 - ch) * fy,
+                     bsh * x[:, 0] + ch * x[:, 2] - bsh * fx,
+                     bsh * x[:, 1] + ch * x[:, 3] - bsh * fy,
+                     x[:, 4] + tt * hp], axis=1)
+
+
+def foot_with_veldes(k, xn, vdes):
+    """cal_foot_with_veldes (MPC_LIP_modi.py:188-194): B_vel^-1 (v_des - (A x)[2:4])."""
+    ax = k["bsh"] * xn[:, 0] + k["ch"] * xn[:, 2]
+    ay = k["bsh"] * xn[:, 1] + k["ch"] * xn[:, 3]
+    return np.stack([k["ibv"] * (vdes[:, 0] - ax), k["ibv"] * (vdes[:, 1] - ay)], 1)
+
+
+def plan_outputs(k, xn, u):
+    """What gen_control_test derives from a solve's u at x_nex (MPC_LIP_modi.py:102-115): p_list[0] (n, 3) and
+    xk_list[1:] (n, N, 5), p_k = W (u_k - A x_k), x_{k+1} = M_A x_k + M_B u_k."""
+    N = k["N"]
+    u = np.asarray(u, float).reshape(len(xn), N, 5)
+    xk = np.asarray(xn, float)
+    foot = (u[:, 0] - xk @ k["A"].T) @ k["W"].T
+    xp = []
+    for j in range(N):
+        xk = xk @ k["M_A"].T + u[:, j] @ k["M_B"].T
+        xp.append(xk)
+    return foot, np.stack(xp, 1)
+
+
+def _rot(th, vx, vy):
+    c, s = np.cos(th), np.sin(th)
+    return c * vx + s * vy, -s * vx + c * vy
+
+
+def command(p0, foot, fx, fy, xn, vdes, hd, hp, hcos, i, F):
+    """The task-space-controller command of a tick (Logger.gen_nex_foot_input / cal_foot_input + gen_tsc_control):
+    foot the next foothold (n, 2) in the map frame, p0 the initial pose (origin and heading of the robot frame)."""
+    nsx, nsy = _rot(p0[:, 2], foot[:, 0] - p0[:, 0], foot[:, 1] - p0[:, 1])
+    csx, csy = _rot(p0[:, 2], fx - p0[:, 0], fy - p0[:, 1])
+    npx, npy = _rot(p0[:, 2], xn[:, 0] - p0[:, 0], xn[:, 1] - p0[:, 1])
+    nvx, nvy = _rot(p0[:, 2], vdes[:, 0], vdes[:, 1])
+    th = hd - p0[:, 2]
+    fi = np.stack(_rot(th, nsx - csx, nsy - csy), -1)
+    npf = np.stack(_rot(th, npx - csx, npy - csy), -1)
+    nvf = np.stack(_rot(th, nvx, nvy), -1)
+    return tsc.gen_tsc_control(fi, npf, nvf, hp, hcos - p0[:, 2], i, F)
+
+
+def _loop(cfg, inp, mask, steps, f_cyc, kick, seed, solve, dev):
+    k = constants(cfg)
+    N, n, variant = k["N"], 5 * k["N"], k["variant"]
+    S, F = int(steps), int(f_cyc)
+    mask = mask_of(mask, F)
+    x = np.array(inp["x0"], np.float64).reshape(-1, 5).copy()
+    B = len(x)
+    pst = np.array(inp["foot0"], np.float64).reshape(B, 2).copy()
+    goal = np.ascontiguousarray(np.broadcast_to(np.asarray(inp["goal"], np.float64), (B, 2)))
+    leg = np.array(np.broadcast_to(np.asarray(inp["leg"]), (B,)), np.int8).copy()
+    nex_turn, hd_pr, hd_cos = np.zeros(B), np.zeros(B), np.zeros(B)
+    mhd = np.repeat(x[:, 4:5], 3, axis=1)      # mpc_hds_list: 0 in the Logger's robot frame = the initial heading
+    plan = np.zeros((B, n))
+    active = np.ones(B, bool)
+    has_plan = np.zeros(B, bool)
+    rclose = np.zeros(B, bool)
+    beta, T = k["beta"], k["T"]
+    dt = T / F
+    ch_d, shb_d, bsh_d = flow_consts(beta, dt)
+    td = dt / T
+    pose0 = np.concatenate([x[:, 0:2], x[:, 4:5]], axis=1).copy()
+    vdes = des_vel(k, leg)
+    foot = np.full((B, S, 3), np.nan)
+    xs = np.zeros((B, S + 1, 5))
+    xs[:, 0] = x
+    hd = np.zeros((B, S, 2))
+    action = np.full((B, S, F, 8), np.nan)
+    plans = np.full((B, S, F, n), np.nan)
+    target = np.full((B, S, F, 2), np.nan)     # the foothold every tick commands: p_list[0][0:2] or the nominal f
+    status = np.full((B, S, F), ROLLOUT_DONE, np.int32)
+    iters = np.zeros((B, S, F), np.int32)
+    stg = np.full(B, -1, np.int32)
+    solves = dict(b=[], s=[], i=[], x_nex=[], leg=[], u0=[])
+    for s in range(S):
+        if dev is not None:   # replay: every step from the device's own touchdown state and its set of episodes
+            x = np.array(dev["x"][:, s], np.float64)
+            active = np.asarray(dev["status"])[:, s, 0] != ROLLOUT_DONE
+        for i in range(F):
+            idx = np.nonzero(active)[0]
+            if len(idx) == 0:
+                continue
+            rest = T - i * (T / F)
+            ch_r, shb_r, bsh_r = flow_consts(beta, rest)
+            tr = rest * (1.0 / T)
+            if i == 0:   # set_stf_head (data_procs/logger.py:266-288) with the plant heading
+                cur = x[idx, 4]
+                hd_cos[idx] = cur
+                nex_turn[idx] = tsc.tube_step(nex_turn[idx], cur)
+                ssum = nex_turn[idx]
+                prev = [cur, mhd[idx, 0], mhd[idx, 1]]
+                for j in range(3):
+                    ssum = ssum + tsc.angle_a_minus_b(mhd[idx, j], prev[j])
+                hd_pr[idx] = ssum / 4.0
+                hd[idx, s, 0], hd[idx, s, 1] = hd_pr[idx], hd_cos[idx]
+            xi, fx, fy, hp = x[idx], pst[idx, 0], pst[idx, 1], hd_pr[idx]
+            xn = flow(xi, fx, fy, hp, ch_r, shb_r, bsh_r, tr)
+            solved = bool(mask >> i & 1)
+            if solved:
+                u0 = np.tile(xn, (1, N))
+                hp_ = has_plan[idx]
+                if variant == VARIANT_SIG_STEP:
+                    pb = plan[idx].reshape(len(idx), N, 5)
+                    u0[hp_] = np.concatenate([pb[:, 1:], pb[:, -1:]], axis=1).reshape(len(idx), n)[hp_]
+                else:
+                    u0[hp_] = plan[idx][hp_]
+                od = (-leg[idx]).astype(np.int8)
+                if dev is not None:
+                    u = np.asarray(dev["plan"])[idx, s, i]
+                    ft, xp = plan_outputs(k, xn, u)
+                    o = dict(u=u, foot=ft, x_pred=xp, status=np.asarray(dev["status"])[idx, s, i],
+                             iters=np.zeros(len(idx), np.int32))
+                    for key, v in (("b", idx), ("s", np.full(len(idx), s)), ("i", np.full(len(idx), i)),
+                                   ("x_nex", xn), ("leg", od), ("u0", u0)):
+                        solves[key].append(v)
+                else:
+                    o = solve(xn, od, u0, idx)
+                status[idx, s, i] = o["status"]
+                iters[idx, s, i] = o["iters"]
+                plan[idx] = o["u"]
+                plans[idx, s, i] = o["u"]
+                has_plan[idx] = True
+                nex_turn[idx] = o["foot"][:, 2]
+                xp = np.asarray(o["x_pred"]).reshape(len(idx), N, 5)
+                mhd[idx, :min(3, N)] = xp[:, :3, 4]
+                d = np.sqrt(((xp[:, :, 0:2] - goal[idx, None, :]) ** 2).sum(-1))
+                close = (d <= 0.35).any(1) if variant == VARIANT_SIG_STEP else d[:, 0] <= 0.15
+                nfoot = np.asarray(o["foot"])[:, 0:2]
+            else:
+                nfoot = foot_with_veldes(k, xn, vdes[idx])
+                status[idx, s, i] = TICK_NOMINAL
+                iters[idx, s, i] = 0
+            target[idx, s, i] = nfoot
+            action[idx, s, i] = command(pose0[idx], nfoot, fx, fy, xn, vdes[idx], xi[:, 4], hp, hd_cos[idx], i, F)
+            if solved:   # vel_des <- mpc_state_tar[0][2:4] after a solve, [1][2:4] at touchdown
+                kv = 1 if (i == F - 1 and N > 1) else 0
+                vdes[idx] = xp[:, kv, 2:4]
+            xa = flow(xi, fx, fy, hp, ch_d, shb_d, bsh_d, td)
+            if kick > 0:
+                for j, b in enumerate(idx):
+                    xa[j, 2] += kick * (2.0 * cl_uniform(seed, int(b), s, i, 0) - 1.0)
+                    xa[j, 3] += kick * (2.0 * cl_uniform(seed, int(b), s, i, 1) - 1.0)
+            x[idx] = xa
+            if i == F - 1:   # touchdown
+                pst[idx] = nfoot
+                leg[idx] = -leg[idx]
+                foot[idx, s, 0:2] = nfoot
+                foot[idx, s, 2] = nex_turn[idx]
+                if not solved:
+                    pl = plan[idx].reshape(len(idx), N, 5)[:, 1 if N > 1 else 0, 2:4]
+                    vdes[idx] = np.where(has_plan[idx, None], pl, des_vel(k, leg[idx]))
+                stop = idx[rclose[idx]]
+                active[stop] = False
+                stg[stop] = s + 1
+            if solved:
+                rclose[idx] |= close
+        xs[:, s + 1] = x
+    out = dict(foot=foot, x=xs, hd=hd, status=status, iters=iters, steps_to_goal=stg, action=action, plan=plans,
+               target=target)
+    if dev is not None:
+        cat = lambda v, shape: np.concatenate(v) if v else np.zeros(shape)   # noqa: E731
+        out["solves"] = dict(b=cat(solves["b"], (0,)).astype(np.int64), s=cat(solves["s"], (0,)).astype(np.int64),
+                             i=cat(solves["i"], (0,)).astype(np.int64), x_nex=cat(solves["x_nex"], (0, 5)),
+                             leg=cat(solves["leg"], (0,)).astype(np.int8), u0=cat(solves["u0"], (0, n)))
+    return out
+
+
+def run(cfg, inputs, mask, solve=None, steps=8, f_cyc=20, kick=0.0, seed=0):
+    """The scheduled loop on the host.  cfg: an object with N, variant, dt, g, H (a Cfg); inputs: dict with x0 (B, 5),
+    foot0 (B, 2), goal, leg; mask: int mask or iterable of solved ticks; solve(x_nex (n, 5), od_ev (n,), u0 (n, 5N),
+    idx (n,) the episodes) -> dict(u, foot, x_pred, status, iters) — not needed for mask 0.  Returns the dict of
+    Solver.closed_loop_schedule (plan included, NaN rows on nominal ticks and after the stop) plus target (B, S, f_cyc,
+    2): the foothold every tick commands."""
+    if solve is None and mask_of(mask, f_cyc):
+        raise ValueError("a schedule with solved ticks needs a solve callable")
+    return _loop(cfg, inputs, mask, steps, f_cyc, float(kick), int(seed), solve, None)
+
+
+def replay(cfg, inputs, mask, x_traj, plan_traj, status_traj, kick=0.0, seed=0):
+    """Every step of a device loop recomputed from the device's own touchdown state x_traj[:, s], the episodes it
+    still ran (status_traj[:, s, 0]) and the plans it recorded (plan_traj), a solve's foothold and predicted states
+    derived from its plan as gen_control_test does (plan_outputs).  Returns foot, hd, x (x[:, s + 1] from
+    x_traj[:, s]), action — the values to hold against the device's — and solves: dict(b, s, i, x_nex, leg, u0), the
+    inputs of every solved tick.  (iters is not replayed; steps_to_goal follows from status.)"""
+    st = np.asarray(status_traj)
+    B, S, F = st.shape
+    dev = dict(x=np.asarray(x_traj, np.float64), plan=np.asarray(plan_traj, np.float64).reshape(B, S, F, -1), status=st)
+    return _loop(cfg, inputs, mask, S, F, float(kick), int(seed), None, dev)

@@ -4739,6 +4739,78 @@ __host__ __device__ inline double cl_uniform(unsigned long long seed, long long 
     return (double)(z >> 11) * (1.0 / 9007199254740992.0);
 }
 
+// The per-tick arithmetic of the loop, stated once for the per-tick kernels (cl_project_kernel, cl_update_kernel) and
+// the nominal-run kernel (cl_nominal_run_kernel).
+// set_stf_head (logger_mpc.py:270-280) with the plant heading cur: hv = nex_turn, hd_input_pr, hd_input_cos
+__device__ inline void cl_set_stf_head(double cur, double* hv, const double* mh)
+{
+    hv[2] = cur;
+    hv[0] = tube_turn(hv[0], cur);
+    double sum = hv[0];
+    const double nc[3] = {cur, mh[0], mh[1]};
+    for (int k = 0; k < 3; ++k) sum += ang_diff(mh[k], nc[k]);
+    hv[1] = sum / 4.0;
+}
+// get_next_states(pos, vel, hd, [foot, hp], t) with the flow constants of t: cosh, sinh / beta, beta sinh, t / T
+__device__ inline void cl_flow(const double* x, double fx, double fy, double hp, double ch, double shb, double bsh,
+                               double tt, double* xn)
+{
+    xn[0] = ch * x[0] + shb * x[2] + (1.0 - ch) * fx;
+    xn[1] = ch * x[1] + shb * x[3] + (1.0 - ch) * fy;
+    xn[2] = bsh * x[0] + ch * x[2] - bsh * fx;
+    xn[3] = bsh * x[1] + ch * x[3] - bsh * fy;
+    xn[4] = x[4] + tt * hp;
+}
+// the plant's velocity kick of (episode, step, tick)
+__device__ inline void cl_kick(double kick, unsigned long long seed, long long b, int s, int i, double* xn)
+{
+    if (kick > 0) {
+        xn[2] += kick * (2.0 * cl_uniform(seed, b, s, i, 0) - 1.0);
+        xn[3] += kick * (2.0 * cl_uniform(seed, b, s, i, 1) - 1.0);
+    }
+}
+// gen_nex_foot_input / cal_foot_input (logger_mpc.py:318-360, logger.py:380-410) + gen_tsc_control (:374-384) for the
+// next foothold nf: robot-global frame = the map frame moved to the initial pose p0 (pos/vel_map_glo_2_robo_glo,
+// :134-150); the foot frame is the stance foot (fx, fy) rotated by the base heading x[4]; xn x_nex of this tick, vd
+// v_des_map, hv nex_turn, hd_input_pr, hd_input_cos.  (Pointers: each value is read where the command uses it.)
+__device__ inline void cl_command(const double* p0, const double* nf, double fx, double fy, const double* xn,
+                                  const double* vd, const double* x, const double* hv, int f, int i, double* a)
+{
+    double s0, c0;
+    sincos(p0[2], &s0, &c0);
+    auto rob = [&](double px, double py, double& rx, double& ry) {
+        const double dx = px - p0[0], dy = py - p0[1];
+        rx = c0 * dx + s0 * dy;
+        ry = -s0 * dx + c0 * dy;
+    };
+    double nsx, nsy, csx, csy, npx, npy;
+    rob(nf[0], nf[1], nsx, nsy);   // nex_stf_rob
+    rob(fx, fy, csx, csy);         // pos_stf_rob_glo_frame
+    rob(xn[0], xn[1], npx, npy);   // nex_pos_rob
+    const double vx = vd[0], vy = vd[1];
+    const double nvx = c0 * vx + s0 * vy, nvy = -s0 * vx + c0 * vy;   // nex_vel_rob
+    double sb, cb;
+    sincos(x[4] - p0[2], &sb, &cb);                         // M_T of hd_base_rob_glo_fram
+    a[0] = cb * (nsx - csx) + sb * (nsy - csy);
+    a[1] = -sb * (nsx - csx) + cb * (nsy - csy);
+    a[2] = 0.0;
+    a[3] = hv[1] / f * (i + 4.5) + (hv[2] - p0[2]);         // hd_input_pr ramp + hd_input_cos (robot frame)
+    a[4] = cb * (npx - csx) + sb * (npy - csy);
+    a[5] = -sb * (npx - csx) + cb * (npy - csy);
+    a[6] = cb * nvx + sb * nvy;
+    a[7] = 0.0;
+    (void)nvy;
+}
+// the lateral part of alip_des_vel(vx, leg_ind) (MPC_LIP_modi.py:181-186), vdy0 = beta sinh(beta T) / (cosh(beta T) + 1)
+__device__ inline double des_vel_y(double leg, double vdy0) { return 0.5 * (-0.5 * leg * 0.3) * vdy0; }
+// one axis of cal_foot_with_veldes (MPC_LIP_modi.py:188-194): B_vel^-1 (vel_des - (A x)[2:4]), bsh = beta sinh(beta T),
+// ch = cosh(beta T), ibv = 1 / (-beta sinh(beta T))
+__device__ inline double veldes_foot(double bsh, double ch, double ibv, double pos, double vel, double vd)
+{
+    const double a = bsh * pos + ch * vel;
+    return ibv * (vd - a);
+}
+
 __global__ __launch_bounds__(256) void cl_project_kernel(CLP C)
 {
     const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -4750,14 +4822,7 @@ __global__ __launch_bounds__(256) void cl_project_kernel(CLP C)
     double* hv = C.hdv + 4 * b;
     const double* mh = C.mhd + 3 * b;
     if (C.i == 0) {
-        // set_stf_head (logger_mpc.py:270-280) with the plant heading
-        const double cur = x[4];
-        hv[2] = cur;
-        hv[0] = tube_turn(hv[0], cur);
-        double sum = hv[0];
-        const double nc[3] = {cur, mh[0], mh[1]};
-        for (int k = 0; k < 3; ++k) sum += ang_diff(mh[k], nc[k]);
-        hv[1] = sum / 4.0;
+        cl_set_stf_head(x[4], hv, mh);
         if (C.hd_traj) {
             C.hd_traj[((size_t)b * C.S + C.s) * 2] = hv[1];
             C.hd_traj[((size_t)b * C.S + C.s) * 2 + 1] = hv[2];
@@ -4766,11 +4831,7 @@ __global__ __launch_bounds__(256) void cl_project_kernel(CLP C)
     // get_next_states(pos, vel, hd, [foot, hd_input_pr], rest_t)
     const double fx = C.pst[2 * b], fy = C.pst[2 * b + 1], hp = hv[1];
     double xn[5];
-    xn[0] = C.ch_r * x[0] + C.shb_r * x[2] + (1.0 - C.ch_r) * fx;
-    xn[1] = C.ch_r * x[1] + C.shb_r * x[3] + (1.0 - C.ch_r) * fy;
-    xn[2] = C.bsh_r * x[0] + C.ch_r * x[2] - C.bsh_r * fx;
-    xn[3] = C.bsh_r * x[1] + C.ch_r * x[3] - C.bsh_r * fy;
-    xn[4] = x[4] + C.tr * hp;
+    cl_flow(x, fx, fy, hp, C.ch_r, C.shb_r, C.bsh_r, C.tr, xn);
     for (int c = 0; c < 5; ++c) C.xs[5 * b + c] = xn[c];
     const int n = 5 * C.N;
     double* g = C.u0 + (size_t)b * n;
@@ -4882,37 +4943,9 @@ __global__ __launch_bounds__(256) void cl_update_kernel(CLP C)
         }
     }
     if (C.ds_nst && C.i == 0) C.ds_nst[b] = C.s + 1;
-    if (C.action_traj) {
-        // gen_nex_foot_input (logger_mpc.py:318-360) + gen_tsc_control (:374-384): robot-global frame = the
-        // map frame moved to the initial pose (pos/vel_map_glo_2_robo_glo, :134-150); the foot frame is the
-        // stance foot rotated by the base heading
-        const double* p0 = C.pose0 + 3 * b;
-        double s0, c0;
-        sincos(p0[2], &s0, &c0);
-        auto rob = [&](double px, double py, double& rx, double& ry) {
-            const double dx = px - p0[0], dy = py - p0[1];
-            rx = c0 * dx + s0 * dy;
-            ry = -s0 * dx + c0 * dy;
-        };
-        double nsx, nsy, csx, csy, npx, npy;
-        rob(C.foot[3 * b], C.foot[3 * b + 1], nsx, nsy);       // nex_stf_rob (p_list[0])
-        rob(fx, fy, csx, csy);                                  // pos_stf_rob_glo_frame
-        rob(C.xs[5 * b], C.xs[5 * b + 1], npx, npy);            // nex_pos_rob (x_nex of this tick)
-        const double vx = C.vdes[2 * b], vy = C.vdes[2 * b + 1];
-        const double nvx = c0 * vx + s0 * vy, nvy = -s0 * vx + c0 * vy;   // nex_vel_rob
-        double sb, cb;
-        sincos(x[4] - p0[2], &sb, &cb);                         // M_T of hd_base_rob_glo_fram
-        double* a = C.action_traj + ti * 8;
-        a[0] = cb * (nsx - csx) + sb * (nsy - csy);
-        a[1] = -sb * (nsx - csx) + cb * (nsy - csy);
-        a[2] = 0.0;
-        a[3] = hv[1] / C.f * (C.i + 4.5) + (hv[2] - p0[2]);    // hd_input_pr ramp + hd_input_cos (robot frame)
-        a[4] = cb * (npx - csx) + sb * (npy - csy);
-        a[5] = -sb * (npx - csx) + cb * (npy - csy);
-        a[6] = cb * nvx + sb * nvy;
-        a[7] = 0.0;
-        (void)nvy;
-    }
+    if (C.action_traj)   // the command of this tick's plan: p_list[0], x_nex and v_des_map before this tick's update
+        cl_command(C.pose0 + 3 * b, C.foot + 3 * b, fx, fy, C.xs + 5 * b, C.vdes + 2 * b, x, hv, C.f, C.i,
+                   C.action_traj + ti * 8);
     // vel_des <- mpc_state_tar[0][2:4] after every solve, [1][2:4] at touchdown (main_sim_mpc.py:88, 112)
     if (C.vdes) {
         const int kv = (C.i == C.f - 1 && C.N > 1) ? 1 : 0;
@@ -4921,15 +4954,8 @@ __global__ __launch_bounds__(256) void cl_update_kernel(CLP C)
     }
     // the plant moves dt around the stance foot (+ the velocity kick)
     double xn[5];
-    xn[0] = C.ch_d * x[0] + C.shb_d * x[2] + (1.0 - C.ch_d) * fx;
-    xn[1] = C.ch_d * x[1] + C.shb_d * x[3] + (1.0 - C.ch_d) * fy;
-    xn[2] = C.bsh_d * x[0] + C.ch_d * x[2] - C.bsh_d * fx;
-    xn[3] = C.bsh_d * x[1] + C.ch_d * x[3] - C.bsh_d * fy;
-    xn[4] = x[4] + C.td * hv[1];
-    if (C.kick > 0) {
-        xn[2] += C.kick * (2.0 * cl_uniform(C.seed, C.b0 + b, C.s, C.i, 0) - 1.0);
-        xn[3] += C.kick * (2.0 * cl_uniform(C.seed, C.b0 + b, C.s, C.i, 1) - 1.0);
-    }
+    cl_flow(x, fx, fy, hv[1], C.ch_d, C.shb_d, C.bsh_d, C.td, xn);
+    cl_kick(C.kick, C.seed, C.b0 + b, C.s, C.i, xn);
     for (int c = 0; c < 5; ++c) x[c] = xn[c];
     if (C.i == C.f - 1) {
         // touchdown: the planned foothold becomes the stance foot, stance switch
@@ -4966,7 +4992,7 @@ __global__ __launch_bounds__(256) void cl_init_kernel(CLP C)
         for (int c = 0; c < 5; ++c) C.x_traj[(size_t)b * (C.S + 1) * 5 + c] = C.x[5 * b + c];
     if (C.vdes) {   // vel_des = alip_des_vel(0.6, leg_ind) (main_sim_mpc.py:54)
         C.vdes[2 * b] = C.vdx;
-        C.vdes[2 * b + 1] = 0.5 * (-0.5 * (double)C.leg[b] * 0.3) * C.vdy0;
+        C.vdes[2 * b + 1] = des_vel_y((double)C.leg[b], C.vdy0);
         C.pose0[3 * b] = C.x[5 * b];
         C.pose0[3 * b + 1] = C.x[5 * b + 1];
         C.pose0[3 * b + 2] = C.x[5 * b + 4];
@@ -4996,15 +5022,140 @@ __global__ __launch_bounds__(256) void nominal_gait_kernel(NgP Q)
         v1 = Q.vin[2 * b + 1];
     } else {
         v0 = Q.vdx;
-        v1 = 0.5 * (-0.5 * (double)Q.leg[b] * 0.3) * Q.vdy0;
+        v1 = des_vel_y((double)Q.leg[b], Q.vdy0);
     }
     if (Q.vout) {
         Q.vout[2 * b] = v0;
         Q.vout[2 * b + 1] = v1;
     }
-    const double ax = Q.bsh * x[0] + Q.ch * x[2], ay = Q.bsh * x[1] + Q.ch * x[3];
-    Q.foot[2 * b] = Q.ibv * (v0 - ax);
-    Q.foot[2 * b + 1] = Q.ibv * (v1 - ay);
+    const double f0 = veldes_foot(Q.bsh, Q.ch, Q.ibv, x[0], x[2], v0);
+    const double f1 = veldes_foot(Q.bsh, Q.ch, Q.ibv, x[1], x[3], v1);
+    Q.foot[2 * b] = f0;
+    Q.foot[2 * b + 1] = f1;
+}
+
+// ------------------------------------------------------------------------------------------------
+// nominal ticks of the scheduled closed loop (alipmpc_closed_loop_schedule_batch): main_sim_mpc_alip.py:96-105,
+// 121-124 driving Logger.cal_foot_input (data_procs/logger.py:380-410).  A tick without a solve projects the plant
+// (cl_project_kernel's x_nex), takes the foothold f = cal_foot_with_veldes(x_nex, v_des_map) (nominal_gait_kernel's
+// expression), packs the command with f in place of p_list[0][0:2] and moves the plant as cl_update_kernel does;
+// nex_turn, mpc_hds_list, the plan, v_des_map and the close flag stay as the last solve left them.  A touchdown on
+// such a tick: stance foot <- f, leg_ind <- -leg_ind, v_des_map <- plan row 1 [2:4] (row 0 at N = 1; alip_des_vel(0.6,
+// leg_ind) before the first solve), then the stop test.
+// One episode per thread over a maximal run of consecutive nominal ticks (it may cross step boundaries): the
+// episode's state is loaded once, kept in registers over the run and stored once; the outputs of every tick are
+// written as the per-tick kernels write them.  The flow constants of each tick index travel by value.
+// ------------------------------------------------------------------------------------------------
+constexpr int CL_MAX_F = 64;   // f_cyc of a scheduled loop: a bit of the mask and a row of CLN::rest per tick
+struct CLN {
+    CLP C;                    // the episode group's arguments (its s, i and rest-flow constants are not read)
+    long long t0;             // first tick of the run, s * f + i
+    int nt;                   // ticks of the run, t0 + nt <= S * f
+    double bsh, ch, ibv;      // cal_foot_with_veldes: beta sinh(beta T), cosh(beta T), 1 / (-beta sinh(beta T))
+    double* plan_traj;        // B x S x f x 5N or NULL: NaN rows on these ticks
+    double rest[CL_MAX_F][4]; // per tick index: cosh, sinh / beta, beta sinh of rest_t, rest_t / T
+};
+
+__global__ __launch_bounds__(256) void cl_nominal_run_kernel(CLN Q)
+{
+    const CLP& C = Q.C;
+    const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= C.B) return;
+    uint8_t fl = C.flags[b];
+    double x[5], hv[3], mh[3], p0[3];
+    for (int c = 0; c < 5; ++c) x[c] = C.x[5 * b + c];
+    for (int c = 0; c < 3; ++c) {
+        hv[c] = C.hdv[4 * b + c];
+        mh[c] = C.mhd[3 * b + c];
+        p0[c] = C.pose0[3 * b + c];
+    }
+    double fx = C.pst[2 * b], fy = C.pst[2 * b + 1], vd[2] = {C.vdes[2 * b], C.vdes[2 * b + 1]};
+    int leg = C.leg[b];
+    const int n = 5 * C.N;
+    int s = (int)(Q.t0 / C.f), i = (int)(Q.t0 - (long long)s * C.f);
+    for (int t = 0; t < Q.nt; ++t) {
+        const size_t si = (size_t)b * C.S + s, ti = si * C.f + i;
+        if (Q.plan_traj)
+            for (int c = 0; c < n; ++c) Q.plan_traj[ti * n + c] = NAN;
+        if (C.iters_traj) C.iters_traj[ti] = 0;
+        if (!(fl & 1)) {   // (the fills of cl_update_kernel)
+            if (C.status_traj) C.status_traj[ti] = ALIPMPC_ROLLOUT_DONE;
+            if (C.action_traj)
+                for (int c = 0; c < 8; ++c) C.action_traj[ti * 8 + c] = NAN;
+            if (i == C.f - 1) {
+                if (C.foot_traj)
+                    for (int c = 0; c < 3; ++c) C.foot_traj[si * 3 + c] = NAN;
+                if (C.x_traj)
+                    for (int c = 0; c < 5; ++c) C.x_traj[((size_t)b * (C.S + 1) + s + 1) * 5 + c] = x[c];
+            }
+        } else {
+            if (C.status_traj) C.status_traj[ti] = ALIPMPC_TICK_NOMINAL;
+            if (i == 0) {
+                cl_set_stf_head(x[4], hv, mh);
+                if (C.hd_traj) {
+                    C.hd_traj[si * 2] = hv[1];
+                    C.hd_traj[si * 2 + 1] = hv[2];
+                }
+            }
+            const double* r = Q.rest[i];
+            double xn[5];
+            cl_flow(x, fx, fy, hv[1], r[0], r[1], r[2], r[3], xn);
+            const double nf[2] = {veldes_foot(Q.bsh, Q.ch, Q.ibv, xn[0], xn[2], vd[0]),
+                                  veldes_foot(Q.bsh, Q.ch, Q.ibv, xn[1], xn[3], vd[1])};
+            if (C.action_traj) cl_command(p0, nf, fx, fy, xn, vd, x, hv, C.f, i, C.action_traj + ti * 8);
+            double xa[5];
+            cl_flow(x, fx, fy, hv[1], C.ch_d, C.shb_d, C.bsh_d, C.td, xa);
+            cl_kick(C.kick, C.seed, C.b0 + b, s, i, xa);
+            for (int c = 0; c < 5; ++c) x[c] = xa[c];
+            if (i == C.f - 1) {   // touchdown on the nominal foothold
+                fx = nf[0];
+                fy = nf[1];
+                leg = -leg;
+                if (C.foot_traj) {
+                    C.foot_traj[si * 3] = nf[0];
+                    C.foot_traj[si * 3 + 1] = nf[1];
+                    C.foot_traj[si * 3 + 2] = hv[0];
+                }
+                if (fl & 2) {
+                    const double* pr = C.plan + (size_t)b * n + (C.N > 1 ? 5 : 0);
+                    vd[0] = pr[2];
+                    vd[1] = pr[3];
+                } else {
+                    vd[0] = C.vdx;
+                    vd[1] = des_vel_y((double)leg, C.vdy0);
+                }
+                if (C.x_traj)
+                    for (int c = 0; c < 5; ++c) C.x_traj[((size_t)b * (C.S + 1) + s + 1) * 5 + c] = x[c];
+                if (fl & 4) {
+                    fl &= (uint8_t)~1u;
+                    if (C.steps_to_goal) C.steps_to_goal[b] = s + 1;
+                }
+            }
+        }
+        if (++i == C.f) {
+            i = 0;
+            ++s;
+        }
+    }
+    for (int c = 0; c < 5; ++c) C.x[5 * b + c] = x[c];
+    for (int c = 0; c < 3; ++c) C.hdv[4 * b + c] = hv[c];
+    C.pst[2 * b] = fx;
+    C.pst[2 * b + 1] = fy;
+    C.vdes[2 * b] = vd[0];
+    C.vdes[2 * b + 1] = vd[1];
+    C.leg[b] = (int8_t)leg;
+    C.flags[b] = fl;
+}
+
+// plan_traj row of a solved tick (after cl_update_kernel): the solve's u, NaN for an episode the tick did not solve
+__global__ __launch_bounds__(256) void cl_plan_kernel(CLP C, double* plan_traj)
+{
+    const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= C.B) return;
+    const int n = 5 * C.N;
+    const size_t ti = ((size_t)b * C.S + C.s) * C.f + C.i;
+    const bool on = C.active[b] != 0;
+    for (int c = 0; c < n; ++c) plan_traj[ti * n + c] = on ? C.u[(size_t)b * n + c] : NAN;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1170,19 +1170,31 @@ struct DsArgs {
     int64_t* row_start;
 };
 
-// both closed-loop entry points.  Without ds the launches, grouping and results are those of alipmpc_closed_loop_batch
-// as it always was: everything the dataset adds is registered after the existing areas and sits behind a test of ds.
+// a schedule of alipmpc_closed_loop_schedule_batch (nullptr: every tick solves, whatever f_cyc is)
+struct SchedArgs {
+    uint64_t mask;       // bit i: tick i of every step solves
+    double* plan_traj;   // B x S x f_cyc x 5N or NULL
+};
+
+// the closed-loop entry points.  Without ds and sch the launches, grouping and results are those of
+// alipmpc_closed_loop_batch as it always was: everything the dataset and the schedule add is registered after the
+// existing areas and sits behind a test of ds / sch.
 static int closed_loop_impl(Handle* h, int64_t B, int32_t S, int32_t f_cyc, double kick, uint64_t seed,
                             const double* x0, const double* foot0, const double* goal, const int8_t* leg,
                             const double* cir, const int32_t* nc, const double* elp, const int32_t* ne,
                             double* foot_traj, double* x_traj, double* hd_traj, int32_t* status_traj,
                             int32_t* iters_traj, int32_t* steps_to_goal, double* action_traj, void* hip_stream,
-                            const DsArgs* ds)
+                            const DsArgs* ds, const SchedArgs* sch = nullptr)
 {
     if (!h) return ALIPMPC_EINVAL;
     const alipmpc_cfg& cf = h->cfg;
     if (cf.variant == ALIPMPC_VARIANT_DD) return fail(h, ALIPMPC_EUNSUPPORTED, "closed loop: LIP variants only");
     if (B < 0 || S < 0 || f_cyc < 1 || !(kick >= 0)) return fail(h, ALIPMPC_EINVAL, "B, S < 0, f_cyc < 1 or kick < 0");
+    if (sch) {
+        if (f_cyc > CL_MAX_F) return fail(h, ALIPMPC_EINVAL, "closed loop schedule: f_cyc outside 1..64");
+        if (f_cyc < 64 && (sch->mask >> f_cyc) != 0)
+            return fail(h, ALIPMPC_EINVAL, "closed loop schedule: mpc_mask has a tick at or above f_cyc");
+    }
     const int ncx = 3 * cf.nc_max + 5 * cf.ne_max + 11;   // columns of X
     if (ds) {
         if (ds->first_index < 0 || ds->first_index > (int64_t)1 << 32 || ds->first_index + B > (int64_t)1 << 32)
@@ -1241,6 +1253,8 @@ static int closed_loop_impl(Handle* h, int64_t B, int32_t S, int32_t f_cyc, doub
     Z.out(C.iters_traj, iters_traj, Bz * Sz * Fz);
     Z.out(C.steps_to_goal, steps_to_goal, Bz);
     Z.out(C.action_traj, action_traj, Bz * Sz * Fz * 8);
+    double* d_plan = nullptr;
+    if (sch) Z.out(d_plan, sch->plan_traj, Bz * Sz * Fz * (size_t)n);
     long long* d_rs = nullptr;
     if (ds) {   // host mode reads row_start back itself (below): the rows are downloaded once their number is known
         if (host || !ds->row_start) Z.work(d_rs, Bz + 1);
@@ -1296,6 +1310,7 @@ static int closed_loop_impl(Handle* h, int64_t B, int32_t S, int32_t f_cyc, doub
         KP P;
         hipStream_t s;
         unsigned g1;
+        double* plan_traj;
     } grp[Handle::MAXG];
     const long long nn = n, SF = (long long)S * f_cyc;
     for (int g = 0; g < G; ++g) {
@@ -1320,6 +1335,7 @@ static int closed_loop_impl(Handle* h, int64_t B, int32_t S, int32_t f_cyc, doub
         grp[g].C = c;
         grp[g].P = q;
         grp[g].g1 = (unsigned)((Bg + 255) / 256);
+        grp[g].plan_traj = d_plan ? d_plan + b0 * SF * nn : nullptr;
         grp[g].s = st;
         if (G > 1) {
             if (!h->gst[g]) HIPCHK(h, hipStreamCreateWithFlags(&h->gst[g], hipStreamNonBlocking));
@@ -1334,8 +1350,42 @@ static int closed_loop_impl(Handle* h, int64_t B, int32_t S, int32_t f_cyc, doub
         HIPCHK(h, hipEventRecord(h->gev[Handle::MAXG], st));
         for (int g = 0; g < G; ++g) HIPCHK(h, hipStreamWaitEvent(grp[g].s, h->gev[Handle::MAXG], 0));
     }
-    for (int s = 0; s < S; ++s) {
+    // a scheduled loop's nominal ticks: the arguments every run shares (the rest-flow constants of every tick index,
+    // by the expressions of the solve ticks below), and whether a maximal run is one launch (ALIPMPC_CL_FUSE=0: a
+    // launch per tick, for the A/B comparison)
+    CLN Qn;
+    bool fuse = true;
+    if (sch) {
+        std::memset(&Qn, 0, sizeof(Qn));
+        Qn.bsh = am.A[10]; Qn.ch = am.ch; Qn.ibv = 1.0 / am.B[6];
         for (int i = 0; i < f_cyc; ++i) {
+            const double rest = T - i * (T / f_cyc);
+            Qn.rest[i][0] = std::cosh(beta * rest); Qn.rest[i][1] = std::sinh(beta * rest) / beta;
+            Qn.rest[i][2] = std::sinh(beta * rest) * beta; Qn.rest[i][3] = rest * (1.0 / T);
+        }
+        const char* fe = std::getenv("ALIPMPC_CL_FUSE");
+        fuse = !(fe && std::strcmp(fe, "0") == 0);
+    }
+    auto solves = [&](int i) { return !sch || ((sch->mask >> i) & 1ull) != 0; };
+    const long long TT = (long long)S * f_cyc;
+    for (long long t = 0; t < TT;) {
+        const int s = (int)(t / f_cyc), i = (int)(t % f_cyc);
+        if (!solves(i)) {   // a run of nominal ticks, possibly across step boundaries: one launch per group
+            long long t1 = t + 1;
+            while (fuse && t1 < TT && !solves((int)(t1 % f_cyc))) ++t1;
+            for (int g = 0; g < G; ++g) {
+                Qn.C = grp[g].C;
+                Qn.t0 = t;
+                Qn.nt = (int)(t1 - t);
+                Qn.plan_traj = grp[g].plan_traj;
+                hipLaunchKernelGGL(cl_nominal_run_kernel, dim3(grp[g].g1), dim3(256), 0, grp[g].s, Qn);
+                HIPCHK(h, hipGetLastError());
+            }
+            t = t1;
+            continue;
+        }
+        ++t;
+        {   // a solve tick, as alipmpc_closed_loop_batch always ran it
             // rest_t = step_t - i * (step_t / f_cyc)   (main_sim_mpc.py:78)
             const double rest = T - i * (T / f_cyc);
             for (int g = 0; g < G; ++g) {
@@ -1371,6 +1421,10 @@ static int closed_loop_impl(Handle* h, int64_t B, int32_t S, int32_t f_cyc, doub
                 HIPCHK(h, launch_solve(h, Pg, sg, h->cl_split_it, h->cl_split_tr));
                 hipLaunchKernelGGL(cl_update_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Cg);
                 HIPCHK(h, hipGetLastError());
+                if (grp[g].plan_traj) {
+                    hipLaunchKernelGGL(cl_plan_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Cg, grp[g].plan_traj);
+                    HIPCHK(h, hipGetLastError());
+                }
             }
         }
     }
@@ -1421,6 +1475,20 @@ int alipmpc_closed_loop_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc,
 {
     return closed_loop_impl((Handle*)handle, B, S, f_cyc, kick, seed, x0, foot0, goal, leg, cir, nc, elp, ne, foot_traj,
                             x_traj, hd_traj, status_traj, iters_traj, steps_to_goal, action_traj, hip_stream, nullptr);
+}
+
+int alipmpc_closed_loop_schedule_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc, uint64_t mpc_mask,
+                                       double kick, uint64_t seed,
+                                       const double* x0, const double* foot0, const double* goal, const int8_t* leg,
+                                       const double* cir, const int32_t* nc, const double* elp, const int32_t* ne,
+                                       double* foot_traj, double* x_traj, double* hd_traj, int32_t* status_traj,
+                                       int32_t* iters_traj, int32_t* steps_to_goal, double* action_traj,
+                                       double* plan_traj, void* hip_stream)
+{
+    const SchedArgs sch{mpc_mask, plan_traj};
+    return closed_loop_impl((Handle*)handle, B, S, f_cyc, kick, seed, x0, foot0, goal, leg, cir, nc, elp, ne, foot_traj,
+                            x_traj, hd_traj, status_traj, iters_traj, steps_to_goal, action_traj, hip_stream, nullptr,
+                            &sch);
 }
 
 int alipmpc_closed_loop_dataset_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc, double kick, uint64_t seed,
