@@ -202,6 +202,32 @@ int alipmpc_solve_batch(void* handle, int64_t B,
                         void* hip_stream);
 
 /*
+ * alipmpc_solve_batch with the plan's first-order sensitivities to the state and the goal, taken from the solve's own
+ * KKT system at the accepted iterate: the barrier KKT conditions differentiated with the barrier
+ * parameter and the prologue's piecewise-constant decisions (obstacle selection, leg parity, whether the detour fires
+ * and to which side) held fixed.  Where the detour fired its chain rule is folded in: the outputs are total
+ * derivatives with respect to the caller's x0 and goal.
+ *   Inputs and the outputs u_out .. iters as alipmpc_solve_batch; they are that call's, bit for bit.
+ *   dfoot   B x 3 x 7      d foot_out / d theta (required)
+ *   du      B x 5N x 7     d u_out / d theta, the canonical u_k = x_{k+1} (may be NULL)
+ *   sens_ok B              1: the derivatives are valid; 0: the instance did not end with status 0 or 1, or its KKT
+ *                          matrix had a non-positive pivot without regularisation — every derivative of the instance
+ *                          is NaN (may be NULL)
+ * Columns theta: 0-4 the components of x0, 5-6 the goal.
+ * One launch of the work-queue form for every B (no split launch).  Wave program, fp64, LIP variants, N <= 5; fp32
+ * handles, lane-program handles, DD and N = 6: ALIPMPC_EUNSUPPORTED.  Host / device pointers as alipmpc_solve_batch.
+ */
+int alipmpc_solve_sens_batch(void* handle, int64_t B,
+                             const double* x0, const double* goal, const int8_t* leg,
+                             const double* cir, const int32_t* nc,
+                             const double* elp, const int32_t* ne,
+                             const double* u0, const double* last_u,
+                             double* u_out, double* foot_out, double* x_pred,
+                             int32_t* status, int32_t* iters,
+                             double* dfoot, double* du, int32_t* sens_ok,
+                             void* hip_stream);
+
+/*
  * Evaluate the NLP callbacks and the set-up at given u (parity / oracle hook).  m_max = N*rows_per_step.
  *   f B, grad B x n, c B x m_max, J B x m_max x n, cl/cu B x m_max, goal_eff B x 2 (after detour),
  *   row_active B x m_max.  Any output may be NULL.

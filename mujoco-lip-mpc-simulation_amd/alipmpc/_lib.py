@@ -44,7 +44,7 @@ class Cfg(ctypes.Structure):
 
 
 EXPORTS = ("alipmpc_default_cfg", "alipmpc_rows_per_step", "alipmpc_num_vars", "alipmpc_create",
-           "alipmpc_solve_batch", "alipmpc_eval_batch", "alipmpc_rollout_batch", "alipmpc_closed_loop_batch",
+           "alipmpc_solve_batch", "alipmpc_solve_sens_batch", "alipmpc_eval_batch", "alipmpc_rollout_batch", "alipmpc_closed_loop_batch",
            "alipmpc_closed_loop_dataset_batch", "alipmpc_closed_loop_schedule_batch", "alipmpc_trace_len",
            "alipmpc_trace_batch", "alipmpc_nominal_gait_batch", "alipmpc_solve_slots", "alipmpc_solve_launches", "alipmpc_lane_handoffs", "alipmpc_solve_program", "alipmpc_last_kernel_ms",
            "alipmpc_build_id", "alipmpc_scenes_batch", "alipmpc_audit_summary_len", "alipmpc_audit_batch",
@@ -87,6 +87,9 @@ def load(build_if_missing=True):
     L.alipmpc_create.restype = ctypes.c_int
     L.alipmpc_solve_batch.argtypes = [P, ctypes.c_int64] + [P] * 15
     L.alipmpc_solve_batch.restype = ctypes.c_int
+    if hasattr(L, "alipmpc_solve_sens_batch"):   # (absent from older dev builds used for A/B timing)
+        L.alipmpc_solve_sens_batch.argtypes = [P, ctypes.c_int64] + [P] * 18
+        L.alipmpc_solve_sens_batch.restype = ctypes.c_int
     L.alipmpc_eval_batch.argtypes = [P, ctypes.c_int64] + [P] * 18
     L.alipmpc_eval_batch.restype = ctypes.c_int
     L.alipmpc_rollout_batch.argtypes = [P, ctypes.c_int64, ctypes.c_int32] + [P] * 16
@@ -306,6 +309,22 @@ class Solver:
                                          _ptr(ne), _ptr(u0), _ptr(lu), _ptr(out["u"]), _ptr(out["foot"]),
                                          _ptr(out["x_pred"]), _ptr(out["status"]), _ptr(out["iters"]), None)
         self._check(rc, "alipmpc_solve_batch")
+        return out
+
+    def solve_sens(self, x0, goal, leg, cir, nc, elp=None, ne=None, u0=None, want_du=True):
+        """solve() with the plan's sensitivities (alipmpc_solve_sens_batch): the dict of solve plus dfoot (B, 3, 7),
+        du (B, 5N, 7) (None unless want_du) and sens_ok (B,) — columns as alipmpc.sensitivity.COLUMNS (x0's five
+        components, then the goal); NaN rows where sens_ok is 0."""
+        B, x0, goal, leg, cir, nc, elp, ne = self._inputs(x0, goal, leg, cir, nc, elp, ne)
+        u0 = np.ascontiguousarray(u0, np.float64).reshape(B, self.n)
+        out = dict(u=np.zeros((B, self.n)), foot=np.zeros((B, 3)), x_pred=np.zeros((B, self.cfg.N, self.sdim)),
+                   status=np.zeros(B, np.int32), iters=np.zeros(B, np.int32), dfoot=np.zeros((B, 3, 7)),
+                   du=np.zeros((B, self.n, 7)) if want_du else None, sens_ok=np.zeros(B, np.int32))
+        rc = self._L.alipmpc_solve_sens_batch(self._h, B, _ptr(x0), _ptr(goal), _ptr(leg), _ptr(cir), _ptr(nc),
+                                              _ptr(elp), _ptr(ne), _ptr(u0), None, _ptr(out["u"]), _ptr(out["foot"]),
+                                              _ptr(out["x_pred"]), _ptr(out["status"]), _ptr(out["iters"]),
+                                              _ptr(out["dfoot"]), _ptr(out["du"]), _ptr(out["sens_ok"]), None)
+        self._check(rc, "alipmpc_solve_sens_batch")
         return out
 
     def eval(self, x0, goal, leg, cir, nc, elp=None, ne=None, u=None, last_u=None, want_J=True):
@@ -592,6 +611,20 @@ class Solver:
             _ptr(out["u"]), _ptr(out.get("foot")), _ptr(out.get("x_pred")), _ptr(out.get("status")),
             _ptr(out.get("iters")), _stream_arg(st))
         self._check(rc, "alipmpc_solve_batch")
+
+    def solve_sens_device(self, inp, out, stream=None):
+        """Asynchronous solve with sensitivities on device tensors: inp as solve_device; out as solve_device plus
+        dfoot (B,3,7) (required), du (B,5N,7) and sens_ok (B,) int32 (either may be absent)."""
+        import torch
+        st = stream if stream is not None else torch.cuda.current_stream()
+        B = inp["x0"].shape[0]
+        rc = self._L.alipmpc_solve_sens_batch(
+            self._h, B, _ptr(inp["x0"]), _ptr(inp["goal"]), _ptr(inp["leg"]), _ptr(inp["cir"]), _ptr(inp["nc"]),
+            _ptr(inp.get("elp")), _ptr(inp.get("ne")), _ptr(inp["u0"]), _ptr(inp.get("last_u")),
+            _ptr(out["u"]), _ptr(out.get("foot")), _ptr(out.get("x_pred")), _ptr(out.get("status")),
+            _ptr(out.get("iters")), _ptr(out["dfoot"]), _ptr(out.get("du")), _ptr(out.get("sens_ok")),
+            _stream_arg(st))
+        self._check(rc, "alipmpc_solve_sens_batch")
 
     def eval_device(self, inp, out, stream=None):
         import torch

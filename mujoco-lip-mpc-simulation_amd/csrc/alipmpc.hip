@@ -1507,6 +1507,7 @@ template <int N, int RPL>
 constexpr bool TEAM_HANDOVER = 3 * WAVE * RPL + 3 <= Dim<N>::NCP * Dim<N>::KLD;
 
 #include "resto_wave.inc"
+#include "sens_wave.inc"
 
 // TM: the team-capable build (split launches with team records, solve_kernel<..., TM = true>): phase 1 also cuts an
 // instance by its line-search trial count, phase 2 runs team records on 4 waves; tm < 0 = member -1 - tm of a team.
@@ -1519,7 +1520,9 @@ constexpr bool TEAM_HANDOVER = 3 * WAVE * RPL + 3 <= Dim<N>::NCP * Dim<N>::KLD;
 // PR: the paired phase-2 build (solve_kernel<..., PR = true>): role 1 = an owner wave, which keeps the top priority
 // for its whole resume; role 2 = a filler wave, whose iteration-based priority stays below the owners' until a
 // restoration of its own.  Without PR the role compiles out.
-template <int N, int KSM, class R, bool Q, bool TM = false, bool RS = false, bool PR = false>
+// SN: the sensitivity build (sens_kernel, alipmpc_solve_sens_batch): after the outputs of an instance, sens_epilogue
+// (sens_wave.inc) differentiates the plan at the accepted iterate.  Without SN none of it is compiled.
+template <int N, int KSM, class R, bool Q, bool TM = false, bool RS = false, bool PR = false, bool SN = false>
 __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, long long b, long long rec = -1,
                                           int tm = 0, int role = 0)
 {
@@ -2746,6 +2749,11 @@ __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, lo
         if (P.status) P.status[b] = status;
         if (P.iters) P.iters[b] = it;
     }
+    if constexpr (SN) {
+        static_assert(sizeof(R) == 8 && !TM && !PR, "the sensitivity build: fp64, one wave per instance");
+        sens_epilogue<N, KSM, RPL>(P, w, G, b, lane, rfl(status) == 0 || rfl(status) == 1, rtype, rk, roi, rv, ra0, ra1,
+                                   zl, zu, idl, idu, mo4, rps, nobs, modi);
+    }
 #undef RELANE
 #undef CK
 #undef HL
@@ -2912,6 +2920,33 @@ __global__ __launch_bounds__(WAVE * (TM ? TEAM_WAVES : PR ? PAIR_WAVES : WAVES_P
         }
         queue_exit(q);
     }
+}
+
+// The sensitivity build of the fp64 wave program (alipmpc_solve_sens_batch): the work-queue form of solve_kernel for
+// every B (no split records), each instance followed by sens_epilogue.  RS as the handle's one-phase solve launch has it,
+// so the solve is that launch's, bit for bit.
+template <int N, int KSM, bool RS>
+__global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK, (solve_waves<KSM, double, RS>())) void sens_kernel(KP Pv)
+{
+    using D = Dim<N>;
+    constexpr int NCP = D::NCP;
+    constexpr int NG = D::NG;
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    KP* Ps = reinterpret_cast<KP*>(smem);
+    double* G = smem + KP_DOUBLES;
+    double* wsb = G + NG * NCP;
+    if (threadIdx.x == 0) *Ps = Pv;
+    for (int i = threadIdx.x; i < NG * NCP; i += blockDim.x) G[i] = Pv.G[i];
+    __syncthreads();
+    const KP& P = *Ps;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+    uint32_t* const q = Pv.queue;
+    for (long long b = next_instance(q); b < Pv.B; b = next_instance(q)) {
+        long long rec = -1;
+        asm volatile("" : "+s"(rec));
+        solve_one<N, KSM, double, true, false, RS, false, true>(P, G, wsb, wv, b, rec);
+    }
+    queue_exit(q);
 }
 
 #include "lane_solve.inc"
@@ -5366,6 +5401,49 @@ void launch_solve(const KP& P0, size_t smem, hipStream_t st, unsigned* res_out)
 #undef ALIP_GO
 }
 
+// the sensitivity build (fp64, N <= 5: n <= 15, the gj_regs domain): the persistent work queue over at most the
+// resident workgroups, whatever B is
+template <int N>
+hipError_t launch_sens_t(const KP& P0, size_t smem, hipStream_t st)
+{
+    if constexpr (Dim<N>::n > ALIP_GJ_MAX_N || Dim<N>::n > 15) {
+        return hipErrorNotSupported;
+    } else {
+        auto go = [&](auto kq) {
+            set_smem((const void*)kq, smem);
+            const unsigned res = resident_blocks((const void*)kq, smem);
+            const unsigned need = (unsigned)((P0.B + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
+            const unsigned grid = res > 0 && res < need ? res : (need > 0 ? need : 1u);
+            hipLaunchKernelGGL(kq, dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), smem, st, P0);
+        };
+#define ALIP_GO(K)                                 \
+    do {                                           \
+        if (P0.resto_ipopt)                        \
+            go(sens_kernel<N, K, true>);           \
+        else                                       \
+            go(sens_kernel<N, K, false>);          \
+    } while (0)
+        if (P0.mo4 <= 16)
+            ALIP_GO(4);
+        else if (P0.mo4 <= 32)
+            ALIP_GO(8);
+        else if (P0.mo4 <= 40)
+            ALIP_GO(10);
+        else if (P0.mo4 <= 48)
+            ALIP_GO(12);
+        else if (P0.mo4 <= 64)
+            ALIP_GO(16);
+        else if (P0.mo4 <= 96)
+            ALIP_GO(24);
+        else if (P0.mo4 <= 128)
+            ALIP_GO(32);
+        else
+            ALIP_GO(48);
+#undef ALIP_GO
+        return hipGetLastError();
+    }
+}
+
 // solve kernels run in the handle's precision (cfg.precision); the eval hook is always fp64
 template <int N>
 hipError_t launch_t(bool solve, bool f32, const KP& P, size_t smem, hipStream_t st, unsigned* res_out)
@@ -5415,11 +5493,16 @@ hipError_t launch_dd(bool solve, const KP& P, size_t smem, hipStream_t st)
     hipError_t launch_dd_##k(bool solve, const KP& P, size_t smem, hipStream_t st)                     \
     {                                                                                                  \
         return launch_dd<k>(solve, P, smem, st);                                                       \
+    }                                                                                                  \
+    hipError_t launch_sens_##k(const KP& P, size_t smem, hipStream_t st)                               \
+    {                                                                                                  \
+        return launch_sens_t<k>(P, smem, st);                                                          \
     }
 #define ALIP_LAUNCH_DECL(k)                                                                            \
     hipError_t launch_lip_##k(bool solve, bool f32, const KP& P, size_t smem, hipStream_t st,          \
                               unsigned* res_out = nullptr);                                            \
-    hipError_t launch_dd_##k(bool solve, const KP& P, size_t smem, hipStream_t st);
+    hipError_t launch_dd_##k(bool solve, const KP& P, size_t smem, hipStream_t st);                    \
+    hipError_t launch_sens_##k(const KP& P, size_t smem, hipStream_t st);
 ALIP_LAUNCH_DECL(1) ALIP_LAUNCH_DECL(2) ALIP_LAUNCH_DECL(3) ALIP_LAUNCH_DECL(4) ALIP_LAUNCH_DECL(5) ALIP_LAUNCH_DECL(6)
 #if ALIP_PART_N(1)
 ALIP_LAUNCHERS(1)

@@ -1082,6 +1082,64 @@ int alipmpc_solve_batch(void* handle, int64_t B, const double* x0, const double*
                      iters, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, hip_stream);
 }
 
+// The solve with its sensitivities (DESIGN.md §3.7): one launch of the sensitivity build's work queue.  Its three
+// outputs reach the kernel in KP's eval-output slots (sens_wave.inc: sens_dfoot, sens_du, sens_okp), which a solve
+// launch leaves unused.
+int alipmpc_solve_sens_batch(void* handle, int64_t B, const double* x0, const double* goal, const int8_t* leg,
+                             const double* cir, const int32_t* nc, const double* elp, const int32_t* ne, const double* u0,
+                             const double* last_u, double* u_out, double* foot_out, double* x_pred, int32_t* status,
+                             int32_t* iters, double* dfoot, double* du, int32_t* sens_ok, void* hip_stream)
+{
+    Handle* h = (Handle*)handle;
+    (void)last_u;   // (DD only, and DD has no sensitivity build)
+    if (!h) return ALIPMPC_EINVAL;
+    const alipmpc_cfg& cf = h->cfg;
+    if (cf.variant == ALIPMPC_VARIANT_DD) return fail(h, ALIPMPC_EUNSUPPORTED, "solve_sens: LIP variants only");
+    if (cf.precision == ALIPMPC_PREC_FP32) return fail(h, ALIPMPC_EUNSUPPORTED, "solve_sens: fp64 handles only");
+    if (h->lane_nct >= 0) return fail(h, ALIPMPC_EUNSUPPORTED, "solve_sens: wave-program handles only");
+    if (h->N > 5) return fail(h, ALIPMPC_EUNSUPPORTED, "solve_sens: N <= 5 (the Gauss-Jordan solve's domain, n <= 15)");
+    if (B < 0) return fail(h, ALIPMPC_EINVAL, "B < 0");
+    if (B == 0) return ALIPMPC_OK;
+    const SceneIn scene{x0, goal, leg, cir, nc, elp, ne, u0};
+    if (!scene_inputs_ok(cf, scene, true)) return fail(h, ALIPMPC_EINVAL, "missing input pointer");
+    if (!u_out || !dfoot) return fail(h, ALIPMPC_EINVAL, "u_out and dfoot are required");
+    if (B >= (int64_t)1 << 31) return fail(h, ALIPMPC_EINVAL, "B >= 2^31 (32-bit work-queue counter)");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int N = h->N;
+    const size_t Bz = (size_t)B;
+    KP P = make_kp(h, B, true);
+    Staging S(h, hip_stream);
+    stage_scene(S, P, h, scene, Bz);
+    S.out(P.u_out, u_out, Bz * 5 * N);
+    S.out(P.foot_out, foot_out, Bz * 3);
+    S.out(P.x_pred, x_pred, Bz * 5 * N);
+    S.out(P.status, status, Bz);
+    S.out(P.iters, iters, Bz);
+    double *d_dfoot = nullptr, *d_du = nullptr;
+    int32_t* d_ok = nullptr;
+    S.out(d_dfoot, dfoot, Bz * 3 * 7);
+    S.out(d_du, du, Bz * 5 * N * 7);
+    S.out(d_ok, sens_ok, Bz);
+    if (int e = S.commit()) return e;
+    P.grad_out = d_dfoot;
+    P.J_out = d_du;
+    P.active_out = reinterpret_cast<int8_t*>(d_ok);
+    TimedSpan span{h, S.st};
+    if (int e = span.begin()) return e;
+    const size_t smem = smem_bytes(h, true);
+    hipError_t le = hipErrorInvalidValue;
+    switch (N) {
+    case 1: le = launch_sens_1(P, smem, S.st); break;
+    case 2: le = launch_sens_2(P, smem, S.st); break;
+    case 3: le = launch_sens_3(P, smem, S.st); break;
+    case 4: le = launch_sens_4(P, smem, S.st); break;
+    case 5: le = launch_sens_5(P, smem, S.st); break;
+    }
+    HIPCHK(h, le);
+    if (int e = span.end()) return e;
+    return S.finish();
+}
+
 int alipmpc_eval_batch(void* handle, int64_t B, const double* x0, const double* goal, const int8_t* leg,
                        const double* cir, const int32_t* nc, const double* elp, const int32_t* ne, const double* u,
                        const double* last_u, double* f, double* grad, double* c, double* J, double* cl, double* cu,
