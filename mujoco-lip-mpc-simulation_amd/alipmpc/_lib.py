@@ -5,7 +5,9 @@ ctypes over the C ABI, numpy arrays for host-pointer calls, torch CUDA tensors (
 for device-pointer calls.  There is no fallback: if the library or a gfx950 device is missing, the
 calls raise.
 """
+import collections
 import ctypes
+import operator
 import os
 
 import numpy as np
@@ -43,12 +45,174 @@ class Cfg(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
-EXPORTS = ("alipmpc_default_cfg", "alipmpc_rows_per_step", "alipmpc_num_vars", "alipmpc_create",
-           "alipmpc_solve_batch", "alipmpc_solve_sens_batch", "alipmpc_eval_batch", "alipmpc_rollout_batch", "alipmpc_closed_loop_batch",
-           "alipmpc_closed_loop_dataset_batch", "alipmpc_closed_loop_schedule_batch", "alipmpc_trace_len",
-           "alipmpc_trace_batch", "alipmpc_nominal_gait_batch", "alipmpc_solve_slots", "alipmpc_solve_launches", "alipmpc_lane_handoffs", "alipmpc_solve_program", "alipmpc_last_kernel_ms",
-           "alipmpc_build_id", "alipmpc_scenes_batch", "alipmpc_audit_summary_len", "alipmpc_audit_batch",
-           "alipmpc_last_error", "alipmpc_destroy")
+# ---------------------------------------------------------------- the ABI, one ordered declaration per export
+# Every export of include/alipmpc.h is stated here once: its return type and its arguments in the header's order.
+# load() sets the ctypes prototypes from this table, Solver._host / Solver._device build every batch call's argument
+# vector from it, and tests/test_binding_host.py holds it against the header.  A new entry point is one row here and
+# a short method on Solver.
+#   Scalar: a by-value argument or a pointer to one value (ctypes type, header name).
+#   Array:  a caller-owned buffer, passed as void*.  key: its name in the wrappers' dicts; out: the library writes it;
+#           opt: a device-mode dict may leave the key out (NULL); nullable: a host-mode None is passed as NULL;
+#           shape: a tuple of ints, names (the solver's n, sdim, m_max, the cfg's N, nc_max, ne_max, the call's scalars
+#           by header name, rows, words) and callables of those, or one callable that gives the tuple, or None for NULL;
+#           bcast: a host input is broadcast to the shape (otherwise reshaped); host: a host pointer in both modes.
+Scalar = collections.namedtuple("Scalar", "ctype name")
+Array = collections.namedtuple("Array", "key dtype out opt nullable shape bcast host")
+Entry = collections.namedtuple("Entry", "restype args")
+
+_int, _i32, _i64, _u64, _f64, _P = (ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double,
+                                    ctypes.c_void_p)
+_f8, _i4, _i1, _i8 = np.float64, np.int32, np.int8, np.int64
+_CFG = Scalar(ctypes.POINTER(Cfg), "cfg")
+_HANDLE, _STREAM, _B = Scalar(_P, "handle"), Scalar(_P, "hip_stream"), Scalar(_i64, "B")
+
+
+def _in(key, dtype, *dims, shape=None, opt=False, nullable=None, bcast=False, host=False):
+    return Array(key, np.dtype(dtype), False, opt, opt if nullable is None else nullable, shape or dims, bcast, host)
+
+
+def _out(key, dtype, *dims, shape=None, opt=True):
+    return Array(key, np.dtype(dtype), True, opt, False, shape or dims, False, False)
+
+
+def _elp_shape(d):   # no ellipse slots: elp and ne are NULL in both directions
+    return (d["B"], d["ne_max"], 5) if d["ne_max"] else None
+
+
+def _ne_shape(d):
+    return (d["B"],) if d["ne_max"] else None
+
+
+def _steps1(d):
+    return d["S"] + 1
+
+
+# x0, goal, leg, cir, nc, elp, ne: the scene block of solve / eval / rollout / audit and, around foot0, the closed loops
+_SCENE = (_in("x0", _f8, "B", "sdim"), _in("goal", _f8, "B", 2, bcast=True),
+          _in("leg", _i1, "B", nullable=True, bcast=True), _in("cir", _f8, "B", "nc_max", 3, bcast=True),
+          _in("nc", _i4, "B", bcast=True),
+          _in("elp", _f8, shape=_elp_shape, opt=True, nullable=False, bcast=True),
+          _in("ne", _i4, shape=_ne_shape, opt=True, nullable=False, bcast=True))
+_LAST_U = _in("last_u", _f8, "B", 2, opt=True, bcast=True)
+_SOLVE_IN = _SCENE + (_in("u0", _f8, "B", "n"), _LAST_U)
+_SOLVE_OUT = (_out("u", _f8, "B", "n", opt=False), _out("foot", _f8, "B", 3), _out("x_pred", _f8, "B", "N", "sdim"),
+              _out("status", _i4, "B"), _out("iters", _i4, "B"))
+_CL_HEAD = (_HANDLE, _B, Scalar(_i32, "S"), Scalar(_i32, "f_cyc"))
+_CL_IN = _SCENE[:1] + (_in("foot0", _f8, "B", 2),) + _SCENE[1:]
+_CL_OUT = (_out("foot", _f8, "B", "S", 3), _out("x", _f8, "B", _steps1, 5), _out("hd", _f8, "B", "S", 2),
+           _out("status", _i4, "B", "S", "f_cyc"), _out("iters", _i4, "B", "S", "f_cyc"),
+           _out("steps_to_goal", _i4, "B"), _out("action", _f8, "B", "S", "f_cyc", 8))
+_KICK_SEED = (Scalar(_f64, "kick"), Scalar(_u64, "seed"))
+
+_ABI = {
+    "alipmpc_default_cfg": Entry(_int, (Scalar(_i32, "variant"), Scalar(_i32, "N"), _CFG._replace(name="out"))),
+    "alipmpc_rows_per_step": Entry(_i32, (_CFG,)),
+    "alipmpc_num_vars": Entry(_i32, (_CFG,)),
+    "alipmpc_create": Entry(_int, (_CFG, Scalar(_int, "device"), Scalar(ctypes.POINTER(_P), "handle"))),
+    "alipmpc_solve_batch": Entry(_int, (_HANDLE, _B) + _SOLVE_IN + _SOLVE_OUT + (_STREAM,)),
+    "alipmpc_solve_sens_batch": Entry(_int, (_HANDLE, _B) + _SOLVE_IN + _SOLVE_OUT + (
+        _out("dfoot", _f8, "B", 3, 7, opt=False), _out("du", _f8, "B", "n", 7), _out("sens_ok", _i4, "B"), _STREAM)),
+    "alipmpc_eval_batch": Entry(_int, (_HANDLE, _B) + _SCENE + (
+        _in("u", _f8, "B", "n"), _LAST_U, _out("f", _f8, "B"), _out("grad", _f8, "B", "n"),
+        _out("c", _f8, "B", "m_max"), _out("J", _f8, "B", "m_max", "n"), _out("cl", _f8, "B", "m_max"),
+        _out("cu", _f8, "B", "m_max"), _out("goal_eff", _f8, "B", 2), _out("row_active", _i1, "B", "m_max"), _STREAM)),
+    "alipmpc_rollout_batch": Entry(_int, (_HANDLE, _B, Scalar(_i32, "S")) + tuple(
+        a._replace(opt=True) if a.key == "leg" else a for a in _SOLVE_IN) + (
+        _out("foot", _f8, "B", "S", 3), _out("x", _f8, "B", _steps1, "sdim"), _out("status", _i4, "B", "S"),
+        _out("iters", _i4, "B", "S"), _out("steps_to_goal", _i4, "B"), _out("u", _f8, "B", "S", "n"), _STREAM)),
+    "alipmpc_closed_loop_batch": Entry(_int, _CL_HEAD + _KICK_SEED + _CL_IN + _CL_OUT + (_STREAM,)),
+    "alipmpc_closed_loop_dataset_batch": Entry(_int, _CL_HEAD + _KICK_SEED + _CL_IN + _CL_OUT + (
+        Scalar(_i64, "first_index"), Scalar(_f64, "safe_dis"), Scalar(_i64, "max_rows"),
+        _out("X", _f8, "rows", lambda d: 3 * d["nc_max"] + 5 * d["ne_max"] + 11),
+        _out("y_mpc", _f8, "rows", 8), _out("y_act", _f8, "rows", 8), _out("row_status", _i4, "rows"),
+        _out("row_start", _i8, lambda d: d["B"] + 1), _STREAM)),
+    "alipmpc_closed_loop_schedule_batch": Entry(_int, _CL_HEAD + (Scalar(_u64, "mpc_mask"),) + _KICK_SEED + _CL_IN + (
+        *_CL_OUT, _out("plan", _f8, "B", "S", "f_cyc", "n"), _STREAM)),
+    "alipmpc_trace_len": Entry(_i32, (_CFG,)),
+    "alipmpc_trace_batch": Entry(_int, (_HANDLE, _B, _in("x0", _f8, "B", 5), _in("u", _f8, "B", "n"),
+                                        _out("trace", _f8, "B", "N", lambda d: trace_len(d["cfg"]), 2, opt=False),
+                                        _STREAM)),
+    "alipmpc_nominal_gait_batch": Entry(_int, (
+        _HANDLE, _B, Scalar(_f64, "vx_max"), _in("x", _f8, "B", 5), _in("leg", _i1, "B", opt=True, bcast=True),
+        _in("vel_des_in", _f8, "B", 2, opt=True, bcast=True), _out("vel_des", _f8, "B", 2),
+        _out("foot", _f8, "B", 2), _STREAM)),
+    "alipmpc_solve_slots": Entry(_int, (_HANDLE, Scalar(ctypes.POINTER(_i64), "slots"))),
+    "alipmpc_solve_launches": Entry(_int, (_HANDLE, _B, Scalar(ctypes.POINTER(_i32), "launches"),
+                                           Scalar(ctypes.POINTER(_i32), "team"))),
+    "alipmpc_lane_handoffs": Entry(_int, (_HANDLE, _STREAM, Scalar(ctypes.POINTER(_i64), "count"))),
+    "alipmpc_solve_program": Entry(ctypes.c_char_p, (_HANDLE,)),
+    "alipmpc_last_kernel_ms": Entry(_f64, (_HANDLE,)),
+    "alipmpc_build_id": Entry(ctypes.c_char_p, ()),
+    "alipmpc_scenes_batch": Entry(_int, (
+        _HANDLE, _B, Scalar(_u64, "seed"), Scalar(_i64, "first_index"), Scalar(_i32, "n_cir"), Scalar(_i32, "n_elp"),
+        Scalar(_i64, "fields"), Scalar(_i32, "max_candidates"), _out("x0", _f8, "B", 5), _out("goal", _f8, "B", 2),
+        _out("leg", _i1, "B"), _out("cir", _f8, "B", "nc_max", 3), _out("nc", _i4, "B"),
+        _out("elp", _f8, shape=_elp_shape), _out("ne", _i4, shape=_ne_shape),
+        _out("u0", _f8, "B", lambda d: 5 * d["N"]), _STREAM)),
+    "alipmpc_audit_summary_len": Entry(_i32, (Scalar(_i32, "n_edges"),)),
+    "alipmpc_audit_batch": Entry(_int, (_HANDLE, _B) + _SCENE + (
+        _in("u", _f8, "B", "n", opt=True), _in("status", _i4, "B", opt=True, bcast=True),
+        _out("metrics", _f8, "B", 5), _out("where", _i4, "B", 3), Scalar(_f64, "viol_tol"),
+        _in("edges", _f8, "n_edges", host=True), Scalar(_i32, "n_edges"),
+        _out("summary", _i8, "words"), _STREAM)),
+    "alipmpc_last_error": Entry(ctypes.c_char_p, (_HANDLE,)),
+    "alipmpc_destroy": Entry(None, (_HANDLE,)),
+}
+EXPORTS = tuple(_ABI)
+
+
+def _shape(a, d):
+    """Array a's shape under the names d (None: the array is NULL)."""
+    s = a.shape(d) if callable(a.shape) else a.shape
+    return s and tuple(d[x] if isinstance(x, str) else x(d) if callable(x) else x for x in s)
+
+
+def _host_array(a, v, d, skip):
+    """What a host-pointer call passes for array a, given v (None: nothing given): the input converted to a's dtype and
+    shape, or a zeroed output; None is NULL."""
+    if a.out and v is not None:          # the caller's own output buffer (audit's summary)
+        return v
+    shape = _shape(a, d)
+    if shape is None or a.key in skip:
+        return None
+    if a.out:
+        return np.zeros(shape, a.dtype)
+    if v is None and a.nullable:
+        return None
+    if not a.bcast:
+        return np.ascontiguousarray(v, a.dtype).reshape(shape)
+    if 0 in shape[1:]:                   # no slots (nc_max == 0): nothing of the argument is read
+        return np.zeros(shape, a.dtype)
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(v), shape), a.dtype)
+
+
+# The exports every build has had.  The others may be absent from an older development build loaded through
+# ALIPMPC_LIB for A/B timing: load() sets no prototype for an absent one, and calling it raises AttributeError.
+_ALWAYS = frozenset("alipmpc_" + k for k in (
+    "default_cfg", "rows_per_step", "num_vars", "create", "solve_batch", "eval_batch", "rollout_batch",
+    "closed_loop_batch", "trace_len", "trace_batch", "last_kernel_ms", "last_error", "destroy"))
+
+
+def _device_plan(args):
+    """What Solver._device needs of a batch entry, precomputed so that a call runs no Python loop over its arguments:
+    the keys it reads from the inp dict and from the out dict, a getter of the required ones of each (it raises the
+    KeyError of a missing one; None: none is required), and `order`, which puts the values gathered as (scalars in
+    header order, inp values, out values) into the header's order between (handle, B) and the stream.  A host array
+    counts as a scalar: its wrapper passes the host pointer."""
+    mid = args[2:-1]
+    scalars = [i for i, a in enumerate(mid) if isinstance(a, Scalar) or a.host]
+    inps = [i for i, a in enumerate(mid) if i not in scalars and not a.out]
+    outs = [i for i, a in enumerate(mid) if i not in scalars and a.out]
+    gathered = scalars + inps + outs
+
+    def need(idx):
+        required = [mid[i].key for i in idx if not mid[i].opt]
+        return operator.itemgetter(*required) if required else None
+    return (tuple(mid[i].key for i in inps), tuple(mid[i].key for i in outs), need(inps), need(outs),
+            operator.itemgetter(*(gathered.index(i) for i in range(len(mid)))))
+
+
+_DEVICE_PLAN = {name: _device_plan(e.args) for name, e in _ABI.items() if name.endswith("_batch")}
 
 _lib = None
 
@@ -76,74 +240,11 @@ def load(build_if_missing=True):
     if not os.path.exists(path):
         raise RuntimeError(f"libalipmpc.so not found at {path}; run alipmpc.build.build()")
     L = ctypes.CDLL(path)
-    P = ctypes.c_void_p
-    L.alipmpc_default_cfg.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(Cfg)]
-    L.alipmpc_default_cfg.restype = ctypes.c_int
-    L.alipmpc_rows_per_step.argtypes = [ctypes.POINTER(Cfg)]
-    L.alipmpc_rows_per_step.restype = ctypes.c_int32
-    L.alipmpc_num_vars.argtypes = [ctypes.POINTER(Cfg)]
-    L.alipmpc_num_vars.restype = ctypes.c_int32
-    L.alipmpc_create.argtypes = [ctypes.POINTER(Cfg), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
-    L.alipmpc_create.restype = ctypes.c_int
-    L.alipmpc_solve_batch.argtypes = [P, ctypes.c_int64] + [P] * 15
-    L.alipmpc_solve_batch.restype = ctypes.c_int
-    if hasattr(L, "alipmpc_solve_sens_batch"):   # (absent from older dev builds used for A/B timing)
-        L.alipmpc_solve_sens_batch.argtypes = [P, ctypes.c_int64] + [P] * 18
-        L.alipmpc_solve_sens_batch.restype = ctypes.c_int
-    L.alipmpc_eval_batch.argtypes = [P, ctypes.c_int64] + [P] * 18
-    L.alipmpc_eval_batch.restype = ctypes.c_int
-    L.alipmpc_rollout_batch.argtypes = [P, ctypes.c_int64, ctypes.c_int32] + [P] * 16
-    L.alipmpc_rollout_batch.restype = ctypes.c_int
-    L.alipmpc_closed_loop_batch.argtypes = [P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
-                                            ctypes.c_uint64] + [P] * 16
-    L.alipmpc_closed_loop_batch.restype = ctypes.c_int
-    if hasattr(L, "alipmpc_closed_loop_dataset_batch"):   # (absent from older dev builds used for A/B timing)
-        L.alipmpc_closed_loop_dataset_batch.argtypes = [P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                        ctypes.c_double, ctypes.c_uint64] + [P] * 15 + \
-                                                       [ctypes.c_int64, ctypes.c_double, ctypes.c_int64] + [P] * 6
-        L.alipmpc_closed_loop_dataset_batch.restype = ctypes.c_int
-    if hasattr(L, "alipmpc_closed_loop_schedule_batch"):   # (absent from older dev builds used for A/B timing)
-        L.alipmpc_closed_loop_schedule_batch.argtypes = [P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                         ctypes.c_uint64, ctypes.c_double, ctypes.c_uint64] + [P] * 17
-        L.alipmpc_closed_loop_schedule_batch.restype = ctypes.c_int
-    L.alipmpc_trace_len.argtypes = [ctypes.POINTER(Cfg)]
-    L.alipmpc_trace_len.restype = ctypes.c_int32
-    L.alipmpc_trace_batch.argtypes = [P, ctypes.c_int64, P, P, P, P]
-    L.alipmpc_trace_batch.restype = ctypes.c_int
-    if hasattr(L, "alipmpc_nominal_gait_batch"):   # (absent from older dev builds used for A/B timing)
-        L.alipmpc_nominal_gait_batch.argtypes = [P, ctypes.c_int64, ctypes.c_double, P, P, P, P, P, P]
-        L.alipmpc_nominal_gait_batch.restype = ctypes.c_int
-    if hasattr(L, "alipmpc_lane_handoffs"):
-        L.alipmpc_lane_handoffs.argtypes = [P, P, ctypes.POINTER(ctypes.c_int64)]
-        L.alipmpc_lane_handoffs.restype = ctypes.c_int
-    if hasattr(L, "alipmpc_solve_launches"):
-        L.alipmpc_solve_launches.argtypes = [P, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32),
-                                             ctypes.POINTER(ctypes.c_int32)]
-        L.alipmpc_solve_launches.restype = ctypes.c_int
-    if hasattr(L, "alipmpc_solve_slots"):     # (absent from older dev builds used for A/B timing)
-        L.alipmpc_solve_slots.argtypes = [P, ctypes.POINTER(ctypes.c_int64)]
-        L.alipmpc_solve_slots.restype = ctypes.c_int
-    if hasattr(L, "alipmpc_solve_program"):
-        L.alipmpc_solve_program.argtypes = [P]
-        L.alipmpc_solve_program.restype = ctypes.c_char_p
-    if hasattr(L, "alipmpc_build_id"):
-        L.alipmpc_build_id.argtypes = []
-        L.alipmpc_build_id.restype = ctypes.c_char_p
-    if hasattr(L, "alipmpc_scenes_batch"):   # (absent from older dev builds used for A/B timing)
-        L.alipmpc_scenes_batch.argtypes = [P, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32,
-                                           ctypes.c_int32, ctypes.c_int64, ctypes.c_int32] + [P] * 9
-        L.alipmpc_scenes_batch.restype = ctypes.c_int
-    if hasattr(L, "alipmpc_audit_batch"):   # (absent from older dev builds used for A/B timing)
-        L.alipmpc_audit_summary_len.argtypes = [ctypes.c_int32]
-        L.alipmpc_audit_summary_len.restype = ctypes.c_int32
-        L.alipmpc_audit_batch.argtypes = [P, ctypes.c_int64] + [P] * 11 + [ctypes.c_double, P, ctypes.c_int32, P, P]
-        L.alipmpc_audit_batch.restype = ctypes.c_int
-    L.alipmpc_last_kernel_ms.argtypes = [P]
-    L.alipmpc_last_kernel_ms.restype = ctypes.c_double
-    L.alipmpc_last_error.argtypes = [P]
-    L.alipmpc_last_error.restype = ctypes.c_char_p
-    L.alipmpc_destroy.argtypes = [P]
-    L.alipmpc_destroy.restype = None
+    for name, entry in _ABI.items():
+        if name in _ALWAYS or hasattr(L, name):    # an absent symbol gets no prototype; one of _ALWAYS raises here
+            f = getattr(L, name)
+            f.argtypes = [a.ctype if isinstance(a, Scalar) else _P for a in entry.args]
+            f.restype = entry.restype
     _lib = L
     return L
 
@@ -213,9 +314,8 @@ def _stream_arg(st):
 def _ptr(a):
     if a is None:
         return None
-    if hasattr(a, "data_ptr"):          # torch tensor (device mode)
-        return ctypes.c_void_p(a.data_ptr())
-    return a.ctypes.data_as(ctypes.c_void_p)
+    data_ptr = getattr(a, "data_ptr", None)          # torch tensor (device mode)
+    return _P(data_ptr()) if data_ptr is not None else a.ctypes.data_as(_P)
 
 
 class Solver:
@@ -281,117 +381,99 @@ class Solver:
         self._check(self._L.alipmpc_lane_handoffs(self._h, st, ctypes.byref(v)), "alipmpc_lane_handoffs")
         return int(v.value)
 
+    # ---------------------------------------------------------------- the two call paths, driven by _ABI
+    def _host(self, name, given, scalars=(), skip=(), **dims):
+        """Host-pointer call of a batch entry: converts the inputs in `given` (key -> array-like) to the table's dtype
+        and shape, allocates every output that is neither in `given` nor in `skip` (those are None), calls, checks,
+        and returns the outputs as a dict in the table's order.  B is scalars["B"] or the leading size of the
+        entry's first array; `dims` adds names for the shape rules (a B there sizes the arrays only).  `given` is the
+        caller's own dict: converted arrays replace what it held."""
+        cfg, args = self.cfg, _ABI[name].args
+        d = dict(n=self.n, sdim=self.sdim, m_max=self.m_max, cfg=cfg, N=cfg.N, nc_max=cfg.nc_max, ne_max=cfg.ne_max,
+                 handle=self._h, hip_stream=None)
+        d.update(scalars, **dims)
+        if "B" not in d:
+            d["B"] = self._batch_size(name, given)
+        argv, res, keep = [], {}, []
+        for a in args:
+            if isinstance(a, Scalar):
+                argv.append(scalars[a.name] if a.name in scalars else d[a.name])
+                continue
+            v = given.get(a.key)
+            if a.host:
+                v, p, _ = _edges_arg(v)
+            else:
+                v = _host_array(a, v, d, skip)
+                p = _ptr(v)
+            if a.out:
+                res[a.key] = v
+            keep.append(v)
+            argv.append(p)
+        self._check(getattr(self._L, name)(*argv), name)
+        return res
+
+    def _batch_size(self, name, given):
+        """B of a host call: the leading size of the entry's first array, which is converted here, once, in `given`."""
+        lead = next(a for a in _ABI[name].args if isinstance(a, Array))
+        x = np.ascontiguousarray(given[lead.key], lead.dtype).reshape(_shape(lead, dict(B=-1, sdim=self.sdim)))
+        given[lead.key] = x
+        return x.shape[0]
+
+    def _device(self, name, inp, out, stream, B, *scalars):
+        """Device-pointer call of a batch entry, asynchronous on `stream` (None: torch's current stream): the pointers
+        of the tensors in the dicts `inp` / `out`; a required key that is missing is a KeyError, an optional one NULL.
+        `scalars`: the entry's scalars after B (and the host pointer of a host array), in the header's order."""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream()
+        inp_keys, out_keys, need_inp, need_out, order = _DEVICE_PLAN[name]
+        if need_inp:
+            need_inp(inp)
+        if need_out:
+            need_out(out)
+        gathered = [*scalars, *map(_ptr, map(inp.get, inp_keys)), *map(_ptr, map(out.get, out_keys))]
+        self._check(getattr(self._L, name)(self._h, B, *order(gathered), _stream_arg(stream)), name)
+
     # ---------------------------------------------------------------- host (numpy) calls
-    def _inputs(self, x0, goal, leg, cir, nc, elp, ne):
-        cfg = self.cfg
-        x0 = np.ascontiguousarray(x0, np.float64).reshape(-1, self.sdim)
-        B = x0.shape[0]
-        goal = np.ascontiguousarray(np.broadcast_to(np.asarray(goal, np.float64), (B, 2)))
-        leg = None if leg is None else np.ascontiguousarray(np.broadcast_to(np.asarray(leg), (B,)), np.int8)
-        cir = np.ascontiguousarray(np.broadcast_to(np.asarray(cir, np.float64), (B, cfg.nc_max, 3))) \
-            if cfg.nc_max else np.zeros((B, 0, 3))
-        nc = np.ascontiguousarray(np.broadcast_to(np.asarray(nc), (B,)), np.int32)
-        if cfg.ne_max:
-            elp = np.ascontiguousarray(np.broadcast_to(np.asarray(elp, np.float64), (B, cfg.ne_max, 5)))
-            ne = np.ascontiguousarray(np.broadcast_to(np.asarray(ne), (B,)), np.int32)
-        else:
-            elp, ne = None, None
-        return B, x0, goal, leg, cir, nc, elp, ne
+    @staticmethod
+    def _scene(x0, goal, leg, cir, nc, elp, ne, **more):
+        return dict(x0=x0, goal=goal, leg=leg, cir=cir, nc=nc, elp=elp, ne=ne, **more)
 
     def solve(self, x0, goal, leg, cir, nc, elp=None, ne=None, u0=None, last_u=None):
         """Solve a batch from host arrays; returns a dict of numpy outputs."""
-        B, x0, goal, leg, cir, nc, elp, ne = self._inputs(x0, goal, leg, cir, nc, elp, ne)
-        u0 = np.ascontiguousarray(u0, np.float64).reshape(B, self.n)
-        lu = None if last_u is None else np.ascontiguousarray(np.broadcast_to(np.asarray(last_u, np.float64), (B, 2)))
-        out = dict(u=np.zeros((B, self.n)), foot=np.zeros((B, 3)), x_pred=np.zeros((B, self.cfg.N, self.sdim)),
-                   status=np.zeros(B, np.int32), iters=np.zeros(B, np.int32))
-        rc = self._L.alipmpc_solve_batch(self._h, B, _ptr(x0), _ptr(goal), _ptr(leg), _ptr(cir), _ptr(nc), _ptr(elp),
-                                         _ptr(ne), _ptr(u0), _ptr(lu), _ptr(out["u"]), _ptr(out["foot"]),
-                                         _ptr(out["x_pred"]), _ptr(out["status"]), _ptr(out["iters"]), None)
-        self._check(rc, "alipmpc_solve_batch")
-        return out
+        return self._host("alipmpc_solve_batch", self._scene(x0, goal, leg, cir, nc, elp, ne, u0=u0, last_u=last_u))
 
     def solve_sens(self, x0, goal, leg, cir, nc, elp=None, ne=None, u0=None, want_du=True):
         """solve() with the plan's sensitivities (alipmpc_solve_sens_batch): the dict of solve plus dfoot (B, 3, 7),
         du (B, 5N, 7) (None unless want_du) and sens_ok (B,) — columns as alipmpc.sensitivity.COLUMNS (x0's five
         components, then the goal); NaN rows where sens_ok is 0."""
-        B, x0, goal, leg, cir, nc, elp, ne = self._inputs(x0, goal, leg, cir, nc, elp, ne)
-        u0 = np.ascontiguousarray(u0, np.float64).reshape(B, self.n)
-        out = dict(u=np.zeros((B, self.n)), foot=np.zeros((B, 3)), x_pred=np.zeros((B, self.cfg.N, self.sdim)),
-                   status=np.zeros(B, np.int32), iters=np.zeros(B, np.int32), dfoot=np.zeros((B, 3, 7)),
-                   du=np.zeros((B, self.n, 7)) if want_du else None, sens_ok=np.zeros(B, np.int32))
-        rc = self._L.alipmpc_solve_sens_batch(self._h, B, _ptr(x0), _ptr(goal), _ptr(leg), _ptr(cir), _ptr(nc),
-                                              _ptr(elp), _ptr(ne), _ptr(u0), None, _ptr(out["u"]), _ptr(out["foot"]),
-                                              _ptr(out["x_pred"]), _ptr(out["status"]), _ptr(out["iters"]),
-                                              _ptr(out["dfoot"]), _ptr(out["du"]), _ptr(out["sens_ok"]), None)
-        self._check(rc, "alipmpc_solve_sens_batch")
-        return out
+        return self._host("alipmpc_solve_sens_batch", self._scene(x0, goal, leg, cir, nc, elp, ne, u0=u0),
+                          skip=() if want_du else ("du",))
 
     def eval(self, x0, goal, leg, cir, nc, elp=None, ne=None, u=None, last_u=None, want_J=True):
-        B, x0, goal, leg, cir, nc, elp, ne = self._inputs(x0, goal, leg, cir, nc, elp, ne)
-        u = np.ascontiguousarray(u, np.float64).reshape(B, self.n)
-        lu = None if last_u is None else np.ascontiguousarray(np.broadcast_to(np.asarray(last_u, np.float64), (B, 2)))
-        mm = self.m_max
-        out = dict(f=np.zeros(B), grad=np.zeros((B, self.n)), c=np.zeros((B, mm)),
-                   J=np.zeros((B, mm, self.n)) if want_J else None, cl=np.zeros((B, mm)), cu=np.zeros((B, mm)),
-                   goal_eff=np.zeros((B, 2)), row_active=np.zeros((B, mm), np.int8))
-        rc = self._L.alipmpc_eval_batch(self._h, B, _ptr(x0), _ptr(goal), _ptr(leg), _ptr(cir), _ptr(nc), _ptr(elp),
-                                        _ptr(ne), _ptr(u), _ptr(lu), _ptr(out["f"]), _ptr(out["grad"]),
-                                        _ptr(out["c"]), _ptr(out["J"]), _ptr(out["cl"]), _ptr(out["cu"]),
-                                        _ptr(out["goal_eff"]), _ptr(out["row_active"]), None)
-        self._check(rc, "alipmpc_eval_batch")
-        return out
+        return self._host("alipmpc_eval_batch", self._scene(x0, goal, leg, cir, nc, elp, ne, u=u, last_u=last_u),
+                          skip=() if want_J else ("J",))
 
     def rollout(self, x0, goal, leg, cir, nc, elp=None, ne=None, u0=None, last_u=None, steps=8):
         """Closed-loop receding-horizon rollout (alipmpc_rollout_batch) from host arrays.  Returns
         dict(foot (B,S,3), x (B,S+1,sdim), status (B,S), iters (B,S), steps_to_goal (B,), u (B,S,n))."""
-        B, x0, goal, leg, cir, nc, elp, ne = self._inputs(x0, goal, leg, cir, nc, elp, ne)
-        u0 = np.ascontiguousarray(u0, np.float64).reshape(B, self.n)
-        lu = None if last_u is None else np.ascontiguousarray(np.broadcast_to(np.asarray(last_u, np.float64), (B, 2)))
-        S = int(steps)
-        out = dict(foot=np.zeros((B, S, 3)), x=np.zeros((B, S + 1, self.sdim)), status=np.zeros((B, S), np.int32),
-                   iters=np.zeros((B, S), np.int32), steps_to_goal=np.zeros(B, np.int32),
-                   u=np.zeros((B, S, self.n)))
-        rc = self._L.alipmpc_rollout_batch(self._h, B, S, _ptr(x0), _ptr(goal), _ptr(leg), _ptr(cir), _ptr(nc),
-                                           _ptr(elp), _ptr(ne), _ptr(u0), _ptr(lu), _ptr(out["foot"]),
-                                           _ptr(out["x"]), _ptr(out["status"]), _ptr(out["iters"]),
-                                           _ptr(out["steps_to_goal"]), _ptr(out["u"]), None)
-        self._check(rc, "alipmpc_rollout_batch")
-        return out
+        return self._host("alipmpc_rollout_batch", self._scene(x0, goal, leg, cir, nc, elp, ne, u0=u0, last_u=last_u),
+                          dict(S=int(steps)))
 
     def closed_loop(self, x0, foot0, goal, leg, cir, nc, elp=None, ne=None, steps=8, f_cyc=40, kick=0.0, seed=0):
         """Closed loop at the reference's control rate (alipmpc_closed_loop_batch): B episodes, up to `steps`
         walking steps, f_cyc solves per step on an ALIP plant with an optional seeded velocity kick.
         Returns dict(foot (B,S,3), x (B,S+1,5), hd (B,S,2), status (B,S,f_cyc), iters (B,S,f_cyc),
         steps_to_goal (B,), action (B,S,f_cyc,8): the controller command of every tick)."""
-        B, x0, goal, leg, cir, nc, elp, ne = self._inputs(x0, goal, leg, cir, nc, elp, ne)
-        foot0 = np.ascontiguousarray(foot0, np.float64).reshape(B, 2)
-        S, F = int(steps), int(f_cyc)
-        out = dict(foot=np.zeros((B, S, 3)), x=np.zeros((B, S + 1, 5)), hd=np.zeros((B, S, 2)),
-                   status=np.zeros((B, S, F), np.int32), iters=np.zeros((B, S, F), np.int32),
-                   steps_to_goal=np.zeros(B, np.int32), action=np.zeros((B, S, F, 8)))
-        rc = self._L.alipmpc_closed_loop_batch(self._h, B, S, F, float(kick), int(seed), _ptr(x0), _ptr(foot0),
-                                               _ptr(goal), _ptr(leg), _ptr(cir), _ptr(nc), _ptr(elp), _ptr(ne),
-                                               _ptr(out["foot"]), _ptr(out["x"]), _ptr(out["hd"]),
-                                               _ptr(out["status"]), _ptr(out["iters"]), _ptr(out["steps_to_goal"]),
-                                               _ptr(out["action"]), None)
-        self._check(rc, "alipmpc_closed_loop_batch")
-        return out
+        return self._host("alipmpc_closed_loop_batch", self._scene(x0, goal, leg, cir, nc, elp, ne, foot0=foot0),
+                          dict(S=int(steps), f_cyc=int(f_cyc), kick=float(kick), seed=int(seed)))
 
     def closed_loop_device(self, inp, out, steps, f_cyc=40, kick=0.0, seed=0, stream=None):
         """Asynchronous closed loop on device tensors: inp x0 (B,5), foot0 (B,2), goal, leg (int8), cir, nc
         [, elp, ne]; out dict with any of foot, x, hd, status, iters, steps_to_goal, action (shapes of
         closed_loop)."""
-        import torch
-        st = stream if stream is not None else torch.cuda.current_stream()
-        B = inp["x0"].shape[0]
-        rc = self._L.alipmpc_closed_loop_batch(
-            self._h, B, int(steps), int(f_cyc), float(kick), int(seed), _ptr(inp["x0"]), _ptr(inp["foot0"]),
-            _ptr(inp["goal"]), _ptr(inp["leg"]), _ptr(inp["cir"]), _ptr(inp["nc"]), _ptr(inp.get("elp")),
-            _ptr(inp.get("ne")), _ptr(out.get("foot")), _ptr(out.get("x")), _ptr(out.get("hd")),
-            _ptr(out.get("status")), _ptr(out.get("iters")), _ptr(out.get("steps_to_goal")), _ptr(out.get("action")),
-            _stream_arg(st))
-        self._check(rc, "alipmpc_closed_loop_batch")
+        self._device("alipmpc_closed_loop_batch", inp, out, stream, inp["x0"].shape[0], int(steps), int(f_cyc),
+                     float(kick), int(seed))
 
     def closed_loop_schedule(self, x0, foot0, goal, leg, cir, nc, elp=None, ne=None, steps=8, f_cyc=20,
                              mpc_ticks=(15,), kick=0.0, seed=0, want_plans=False):
@@ -401,35 +483,17 @@ class Solver:
         is the reference's hybrid driver (main_sim_mpc_alip.py: 20 ticks, one solve at tick 15).  Returns the dict of
         closed_loop plus plan: (B, S, f_cyc, 5N) the u of every solved tick, NaN elsewhere (None unless want_plans)."""
         from .schedule import mask_of
-        S, F = int(steps), int(f_cyc)
-        mask = mask_of(mpc_ticks)
-        B, x0, goal, leg, cir, nc, elp, ne = self._inputs(x0, goal, leg, cir, nc, elp, ne)
-        foot0 = np.ascontiguousarray(foot0, np.float64).reshape(B, 2)
-        out = dict(foot=np.zeros((B, S, 3)), x=np.zeros((B, S + 1, 5)), hd=np.zeros((B, S, 2)),
-                   status=np.zeros((B, S, F), np.int32), iters=np.zeros((B, S, F), np.int32),
-                   steps_to_goal=np.zeros(B, np.int32), action=np.zeros((B, S, F, 8)),
-                   plan=np.zeros((B, S, F, self.n)) if want_plans else None)
-        rc = self._L.alipmpc_closed_loop_schedule_batch(
-            self._h, B, S, F, mask, float(kick), int(seed), _ptr(x0), _ptr(foot0), _ptr(goal), _ptr(leg), _ptr(cir),
-            _ptr(nc), _ptr(elp), _ptr(ne), _ptr(out["foot"]), _ptr(out["x"]), _ptr(out["hd"]), _ptr(out["status"]),
-            _ptr(out["iters"]), _ptr(out["steps_to_goal"]), _ptr(out["action"]), _ptr(out["plan"]), None)
-        self._check(rc, "alipmpc_closed_loop_schedule_batch")
-        return out
+        sc = dict(S=int(steps), f_cyc=int(f_cyc), mpc_mask=mask_of(mpc_ticks), kick=float(kick), seed=int(seed))
+        return self._host("alipmpc_closed_loop_schedule_batch",
+                          self._scene(x0, goal, leg, cir, nc, elp, ne, foot0=foot0), sc,
+                          skip=() if want_plans else ("plan",))
 
     def closed_loop_schedule_device(self, inp, out, steps, f_cyc=20, mpc_ticks=(15,), kick=0.0, seed=0, stream=None):
         """Asynchronous scheduled closed loop on device tensors: inp / out as closed_loop_device, out also with plan
         (B, S, f_cyc, 5N) if the plans are wanted."""
-        import torch
         from .schedule import mask_of
-        st = stream if stream is not None else torch.cuda.current_stream()
-        B = inp["x0"].shape[0]
-        rc = self._L.alipmpc_closed_loop_schedule_batch(
-            self._h, B, int(steps), int(f_cyc), mask_of(mpc_ticks), float(kick), int(seed), _ptr(inp["x0"]),
-            _ptr(inp["foot0"]), _ptr(inp["goal"]), _ptr(inp["leg"]), _ptr(inp["cir"]), _ptr(inp["nc"]),
-            _ptr(inp.get("elp")), _ptr(inp.get("ne")), _ptr(out.get("foot")), _ptr(out.get("x")), _ptr(out.get("hd")),
-            _ptr(out.get("status")), _ptr(out.get("iters")), _ptr(out.get("steps_to_goal")), _ptr(out.get("action")),
-            _ptr(out.get("plan")), _stream_arg(st))
-        self._check(rc, "alipmpc_closed_loop_schedule_batch")
+        self._device("alipmpc_closed_loop_schedule_batch", inp, out, stream, inp["x0"].shape[0], int(steps), int(f_cyc),
+                     mask_of(mpc_ticks), float(kick), int(seed))
 
     def x_cols(self):
         """Columns of the dataset's X: 3 nc_max + 5 ne_max + 11 (include/alipmpc.h)."""
@@ -443,23 +507,14 @@ class Solver:
         trimmed to the total R = row_start[B].  `first`: global index of episode 0 (the kick stream's episode id).
         max_rows (default B * steps * f_cyc, which always suffices) caps the rows written; rows past it are lost and
         R = min(row_start[B], max_rows)."""
-        B, x0, goal, leg, cir, nc, elp, ne = self._inputs(x0, goal, leg, cir, nc, elp, ne)
-        foot0 = np.ascontiguousarray(foot0, np.float64).reshape(B, 2)
+        given = self._scene(x0, goal, leg, cir, nc, elp, ne, foot0=foot0)
+        B = self._batch_size("alipmpc_closed_loop_dataset_batch", given)
         S, F = int(steps), int(f_cyc)
         cap = B * S * F if max_rows is None else int(max_rows)
         n = max(cap, 0)
-        out = dict(foot=np.zeros((B, S, 3)), x=np.zeros((B, S + 1, 5)), hd=np.zeros((B, S, 2)),
-                   status=np.zeros((B, S, F), np.int32), iters=np.zeros((B, S, F), np.int32),
-                   steps_to_goal=np.zeros(B, np.int32), action=np.zeros((B, S, F, 8)),
-                   X=np.zeros((n, self.x_cols())), y_mpc=np.zeros((n, 8)), y_act=np.zeros((n, 8)),
-                   row_status=np.zeros(n, np.int32), row_start=np.zeros(B + 1, np.int64))
-        rc = self._L.alipmpc_closed_loop_dataset_batch(
-            self._h, B, S, F, float(kick), int(seed), _ptr(x0), _ptr(foot0), _ptr(goal), _ptr(leg), _ptr(cir),
-            _ptr(nc), _ptr(elp), _ptr(ne), _ptr(out["foot"]), _ptr(out["x"]), _ptr(out["hd"]), _ptr(out["status"]),
-            _ptr(out["iters"]), _ptr(out["steps_to_goal"]), _ptr(out["action"]), int(first), float(safe_dis), cap,
-            _ptr(out["X"]), _ptr(out["y_mpc"]), _ptr(out["y_act"]), _ptr(out["row_status"]), _ptr(out["row_start"]),
-            None)
-        self._check(rc, "alipmpc_closed_loop_dataset_batch")
+        out = self._host("alipmpc_closed_loop_dataset_batch", given,
+                         dict(S=S, f_cyc=F, kick=float(kick), seed=int(seed), first_index=int(first),
+                              safe_dis=float(safe_dis), max_rows=cap), B=B, rows=n)
         R = min(int(out["row_start"][B]), n)
         for k in ("X", "y_mpc", "y_act", "row_status"):
             out[k] = out[k][:R]
@@ -471,43 +526,22 @@ class Solver:
         of X (max_rows, 3 nc_max + 5 ne_max + 11), y_mpc (max_rows, 8), y_act (max_rows, 8), row_status (max_rows,)
         int32, row_start (B + 1,) int64.  max_rows defaults to the leading size of the first row tensor given.  Rows
         at positions >= max_rows are not written; the caller reads row_start[B] once the stream is done."""
-        import torch
-        st = stream if stream is not None else torch.cuda.current_stream()
-        B = inp["x0"].shape[0]
         if max_rows is None:
             rows = [out[k] for k in ("X", "y_mpc", "y_act", "row_status") if out.get(k) is not None]
             max_rows = min(t.shape[0] for t in rows) if rows else 0
-        rc = self._L.alipmpc_closed_loop_dataset_batch(
-            self._h, B, int(steps), int(f_cyc), float(kick), int(seed), _ptr(inp["x0"]), _ptr(inp["foot0"]),
-            _ptr(inp["goal"]), _ptr(inp["leg"]), _ptr(inp["cir"]), _ptr(inp["nc"]), _ptr(inp.get("elp")),
-            _ptr(inp.get("ne")), _ptr(out.get("foot")), _ptr(out.get("x")), _ptr(out.get("hd")),
-            _ptr(out.get("status")), _ptr(out.get("iters")), _ptr(out.get("steps_to_goal")), _ptr(out.get("action")),
-            int(first), float(safe_dis), int(max_rows), _ptr(out.get("X")), _ptr(out.get("y_mpc")),
-            _ptr(out.get("y_act")), _ptr(out.get("row_status")), _ptr(out.get("row_start")), _stream_arg(st))
-        self._check(rc, "alipmpc_closed_loop_dataset_batch")
+        self._device("alipmpc_closed_loop_dataset_batch", inp, out, stream, inp["x0"].shape[0], int(steps), int(f_cyc),
+                     float(kick), int(seed), int(first), float(safe_dis), int(max_rows))
 
     def nominal_gait(self, x, leg=None, vx_max=0.6, vel_des=None):
         """Nominal gait (alipmpc_nominal_gait_batch): returns (vel_des (B,2), foot (B,2)) — alip_des_vel(vx_max,
         leg_ind) per instance (or the given vel_des) and cal_foot_with_veldes(x, vel_des)."""
-        x = np.ascontiguousarray(x, np.float64).reshape(-1, 5)
-        B = x.shape[0]
-        lg = None if leg is None else np.ascontiguousarray(np.broadcast_to(np.asarray(leg), (B,)), np.int8)
-        vin = None if vel_des is None else np.ascontiguousarray(np.broadcast_to(vel_des, (B, 2)), np.float64)
-        vout, foot = np.zeros((B, 2)), np.zeros((B, 2))
-        rc = self._L.alipmpc_nominal_gait_batch(self._h, B, float(vx_max), _ptr(x), _ptr(lg), _ptr(vin), _ptr(vout),
-                                                _ptr(foot), None)
-        self._check(rc, "alipmpc_nominal_gait_batch")
-        return vout, foot
+        out = self._host("alipmpc_nominal_gait_batch", dict(x=x, leg=leg, vel_des_in=vel_des),
+                         dict(vx_max=float(vx_max)))
+        return out["vel_des"], out["foot"]
 
     def trace(self, x0, u):
         """Dense plan traces (alipmpc_trace_batch): x0 (B,5), u (B,5N) -> (B, N, trace_len, 2)."""
-        x0 = np.ascontiguousarray(x0, np.float64).reshape(-1, 5)
-        B = x0.shape[0]
-        u = np.ascontiguousarray(u, np.float64).reshape(B, self.n)
-        out = np.zeros((B, self.cfg.N, trace_len(self.cfg), 2))
-        rc = self._L.alipmpc_trace_batch(self._h, B, _ptr(x0), _ptr(u), _ptr(out), None)
-        self._check(rc, "alipmpc_trace_batch")
-        return out
+        return self._host("alipmpc_trace_batch", dict(x0=x0, u=u))["trace"]
 
     def audit(self, x0, goal, leg, cir, nc, elp=None, ne=None, u=None, status=None, edges=(), viol_tol=1e-4,
               summary=None):
@@ -515,125 +549,61 @@ class Solver:
         Returns dict(metrics (B,5), where (B,3), summary (audit_summary_len(len(edges)),) int64) — columns and words
         as alipmpc.audit.COLS / WHERE / SUMMARY_FIELDS (include/alipmpc.h).  The summary counts from zero, or is added
         to a copy of `summary` when one is given (the buffer a chunked sweep carries along)."""
-        B, x0, goal, leg, cir, nc, elp, ne = self._inputs(x0, goal, leg, cir, nc, elp, ne)
-        u = None if u is None else np.ascontiguousarray(u, np.float64).reshape(B, self.n)
-        st = None if status is None else np.ascontiguousarray(np.broadcast_to(np.asarray(status), (B,)), np.int32)
-        e, ep, ne_ = _edges_arg(edges)
-        words = 6 + ne_ + 1 + 20
-        acc = np.zeros(words, np.int64) if summary is None else np.array(summary, np.int64).reshape(-1)
-        if acc.size != words:
-            raise ValueError(f"summary has {acc.size} words, {words} expected for {ne_} edges")
-        out = dict(metrics=np.zeros((B, 5)), where=np.zeros((B, 3), np.int32), summary=acc)
-        rc = self._L.alipmpc_audit_batch(self._h, B, _ptr(x0), _ptr(goal), _ptr(leg), _ptr(cir), _ptr(nc), _ptr(elp),
-                                         _ptr(ne), _ptr(u), _ptr(st), _ptr(out["metrics"]), _ptr(out["where"]),
-                                         float(viol_tol), ep, ne_, _ptr(out["summary"]), None)
-        self._check(rc, "alipmpc_audit_batch")
-        return out
+        ne_ = int(np.size(edges))
+        words = int(self._L.alipmpc_audit_summary_len(ne_))     # negative for an edge count the call itself refuses
+        given = self._scene(x0, goal, leg, cir, nc, elp, ne, u=u, status=status, edges=edges)
+        if summary is not None:
+            given["summary"] = acc = np.array(summary, np.int64).reshape(-1)
+            if words >= 0 and acc.size != words:
+                raise ValueError(f"summary has {acc.size} words, {words} expected for {ne_} edges")
+        return self._host("alipmpc_audit_batch", given, dict(viol_tol=float(viol_tol), n_edges=ne_),
+                          words=max(words, 0))
 
     def audit_device(self, inp, out, edges=(), viol_tol=1e-4, stream=None):
         """Asynchronous plan audit on device tensors: inp as solve_device's plus u (B,5N) the plans and optionally
         status (B,) int32; out any of metrics (B,5) float64, where (B,3) int32, summary (audit_summary_len(len(edges)),)
         int64 — the summary is ADDED to, so one tensor carried through the chunks of a sweep ends as the sweep's.
         edges is a host sequence (copied into the launch)."""
-        import torch
-        st = stream if stream is not None else torch.cuda.current_stream()
-        B = inp["x0"].shape[0]
         e, ep, ne_ = _edges_arg(edges)
-        rc = self._L.alipmpc_audit_batch(
-            self._h, B, _ptr(inp["x0"]), _ptr(inp["goal"]), _ptr(inp["leg"]), _ptr(inp["cir"]), _ptr(inp["nc"]),
-            _ptr(inp.get("elp")), _ptr(inp.get("ne")), _ptr(inp.get("u")), _ptr(inp.get("status")),
-            _ptr(out.get("metrics")), _ptr(out.get("where")), float(viol_tol), ep, ne_, _ptr(out.get("summary")),
-            _stream_arg(st))
-        self._check(rc, "alipmpc_audit_batch")
+        self._device("alipmpc_audit_batch", inp, out, stream, inp["x0"].shape[0], float(viol_tol), ep, ne_)
 
     def scenes(self, B, seed=0, first=0, n_cir=None, n_elp=0, fields=0, max_candidates=0):
         """Monte-Carlo scenes first .. first + B - 1 of the counter-based stream (alipmpc_scenes_batch), generated
         on the device: the dict of scenes.make_batch (elp / ne None without ellipse slots).  n_cir defaults to the
         handle's nc_max; fields > 0 shares that many obstacle fields (instance g uses field g % fields)."""
-        cfg, B = self.cfg, int(B)
-        n_cir = cfg.nc_max if n_cir is None else n_cir
-        Bn = max(B, 0)
-        out = dict(x0=np.zeros((Bn, 5)), goal=np.zeros((Bn, 2)), leg=np.zeros(Bn, np.int8),
-                   cir=np.zeros((Bn, cfg.nc_max, 3)), nc=np.zeros(Bn, np.int32),
-                   elp=np.zeros((Bn, cfg.ne_max, 5)) if cfg.ne_max else None,
-                   ne=np.zeros(Bn, np.int32) if cfg.ne_max else None, u0=np.zeros((Bn, 5 * cfg.N)))
-        rc = self._L.alipmpc_scenes_batch(self._h, B, int(seed), int(first), int(n_cir), int(n_elp), int(fields),
-                                          int(max_candidates), _ptr(out["x0"]), _ptr(out["goal"]), _ptr(out["leg"]),
-                                          _ptr(out["cir"]), _ptr(out["nc"]), _ptr(out["elp"]), _ptr(out["ne"]),
-                                          _ptr(out["u0"]), None)
-        self._check(rc, "alipmpc_scenes_batch")
-        return out
+        n_cir = self.cfg.nc_max if n_cir is None else n_cir
+        return self._host("alipmpc_scenes_batch", {},
+                          dict(B=int(B), seed=int(seed), first_index=int(first), n_cir=int(n_cir), n_elp=int(n_elp),
+                               fields=int(fields), max_candidates=int(max_candidates)), B=max(int(B), 0))
 
     # ---------------------------------------------------------------- device (torch) calls
     def scenes_device(self, out, seed=0, first=0, n_cir=None, n_elp=0, fields=0, max_candidates=0, stream=None):
         """Asynchronous scene generation into device tensors: out holds any of x0 (B,5), goal (B,2), leg (int8),
         cir (B,nc_max,3), nc (int32), elp (B,ne_max,5), ne (int32), u0 (B,5N) — the keys of solve_device's inp, so
         the solve reads what this wrote, on the same stream, with no copy.  B is the leading size of out's tensors."""
-        import torch
-        st = stream if stream is not None else torch.cuda.current_stream()
         B = next(v for v in out.values() if v is not None).shape[0]
         n_cir = self.cfg.nc_max if n_cir is None else n_cir
-        rc = self._L.alipmpc_scenes_batch(
-            self._h, B, int(seed), int(first), int(n_cir), int(n_elp), int(fields), int(max_candidates),
-            _ptr(out.get("x0")), _ptr(out.get("goal")), _ptr(out.get("leg")), _ptr(out.get("cir")),
-            _ptr(out.get("nc")), _ptr(out.get("elp")), _ptr(out.get("ne")), _ptr(out.get("u0")), _stream_arg(st))
-        self._check(rc, "alipmpc_scenes_batch")
+        self._device("alipmpc_scenes_batch", {}, out, stream, B, int(seed), int(first), int(n_cir), int(n_elp),
+                     int(fields), int(max_candidates))
 
     def rollout_device(self, inp, out, steps, stream=None):
         """Asynchronous rollout on device tensors: inp as solve_device, out dict with any of foot (B,S,3),
         x (B,S+1,sdim), status (B,S), iters (B,S), steps_to_goal (B,), u (B,S,n)."""
-        import torch
-        st = stream if stream is not None else torch.cuda.current_stream()
-        B = inp["x0"].shape[0]
-        rc = self._L.alipmpc_rollout_batch(
-            self._h, B, int(steps), _ptr(inp["x0"]), _ptr(inp["goal"]), _ptr(inp.get("leg")), _ptr(inp["cir"]),
-            _ptr(inp["nc"]), _ptr(inp.get("elp")), _ptr(inp.get("ne")), _ptr(inp["u0"]), _ptr(inp.get("last_u")),
-            _ptr(out.get("foot")), _ptr(out.get("x")), _ptr(out.get("status")), _ptr(out.get("iters")),
-            _ptr(out.get("steps_to_goal")), _ptr(out.get("u")), _stream_arg(st))
-        self._check(rc, "alipmpc_rollout_batch")
+        self._device("alipmpc_rollout_batch", inp, out, stream, inp["x0"].shape[0], int(steps))
 
     def trace_device(self, x0, u, trace, stream=None):
         """Asynchronous dense plan traces on device tensors x0 (B,5), u (B,5N) -> trace (B,N,trace_len,2)."""
-        import torch
-        st = stream if stream is not None else torch.cuda.current_stream()
-        rc = self._L.alipmpc_trace_batch(self._h, x0.shape[0], _ptr(x0), _ptr(u), _ptr(trace), _stream_arg(st))
-        self._check(rc, "alipmpc_trace_batch")
+        self._device("alipmpc_trace_batch", {"x0": x0, "u": u}, {"trace": trace}, stream, x0.shape[0])
 
     def solve_device(self, inp, out, stream=None):
         """Asynchronous solve on device tensors.  inp/out: dicts of torch CUDA tensors with the shapes of
         solve(); stream: torch.cuda.Stream (defaults to the current stream)."""
-        import torch
-        st = stream if stream is not None else torch.cuda.current_stream()
-        B = inp["x0"].shape[0]
-        rc = self._L.alipmpc_solve_batch(
-            self._h, B, _ptr(inp["x0"]), _ptr(inp["goal"]), _ptr(inp["leg"]), _ptr(inp["cir"]), _ptr(inp["nc"]),
-            _ptr(inp.get("elp")), _ptr(inp.get("ne")), _ptr(inp["u0"]), _ptr(inp.get("last_u")),
-            _ptr(out["u"]), _ptr(out.get("foot")), _ptr(out.get("x_pred")), _ptr(out.get("status")),
-            _ptr(out.get("iters")), _stream_arg(st))
-        self._check(rc, "alipmpc_solve_batch")
+        self._device("alipmpc_solve_batch", inp, out, stream, inp["x0"].shape[0])
 
     def solve_sens_device(self, inp, out, stream=None):
         """Asynchronous solve with sensitivities on device tensors: inp as solve_device; out as solve_device plus
         dfoot (B,3,7) (required), du (B,5N,7) and sens_ok (B,) int32 (either may be absent)."""
-        import torch
-        st = stream if stream is not None else torch.cuda.current_stream()
-        B = inp["x0"].shape[0]
-        rc = self._L.alipmpc_solve_sens_batch(
-            self._h, B, _ptr(inp["x0"]), _ptr(inp["goal"]), _ptr(inp["leg"]), _ptr(inp["cir"]), _ptr(inp["nc"]),
-            _ptr(inp.get("elp")), _ptr(inp.get("ne")), _ptr(inp["u0"]), _ptr(inp.get("last_u")),
-            _ptr(out["u"]), _ptr(out.get("foot")), _ptr(out.get("x_pred")), _ptr(out.get("status")),
-            _ptr(out.get("iters")), _ptr(out["dfoot"]), _ptr(out.get("du")), _ptr(out.get("sens_ok")),
-            _stream_arg(st))
-        self._check(rc, "alipmpc_solve_sens_batch")
+        self._device("alipmpc_solve_sens_batch", inp, out, stream, inp["x0"].shape[0])
 
     def eval_device(self, inp, out, stream=None):
-        import torch
-        st = stream if stream is not None else torch.cuda.current_stream()
-        B = inp["x0"].shape[0]
-        rc = self._L.alipmpc_eval_batch(
-            self._h, B, _ptr(inp["x0"]), _ptr(inp["goal"]), _ptr(inp["leg"]), _ptr(inp["cir"]), _ptr(inp["nc"]),
-            _ptr(inp.get("elp")), _ptr(inp.get("ne")), _ptr(inp["u"]), _ptr(inp.get("last_u")),
-            _ptr(out.get("f")), _ptr(out.get("grad")), _ptr(out.get("c")), _ptr(out.get("J")), _ptr(out.get("cl")),
-            _ptr(out.get("cu")), _ptr(out.get("goal_eff")), _ptr(out.get("row_active")),
-            _stream_arg(st))
-        self._check(rc, "alipmpc_eval_batch")
+        self._device("alipmpc_eval_batch", inp, out, stream, inp["x0"].shape[0])
