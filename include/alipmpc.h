@@ -156,8 +156,17 @@ typedef struct alipmpc_cfg {
                            precisions) and fp32 wave program: an instance whose search fails is handed to the fp64
                            wave program, which solves it from its start (alipmpc_lane_handoffs counts them); the fp64
                            workspace must then fit the LDS too (alipmpc_create: ALIPMPC_EUNSUPPORTED otherwise). */
-    int32_t reserved_;  /* zero */
+    int32_t cl_between;    /* what a tick of alipmpc_closed_loop_schedule_batch that does not solve commands (no other
+                           entry point reads it): ALIPMPC_CL_BETWEEN_NOMINAL (0, default) — the nominal ALIP foothold;
+                           ALIPMPC_CL_BETWEEN_FIRST_ORDER (1) — the last solve's plan moved to first order with the
+                           plant, where that solve's sensitivities are valid (see that entry point).  Mode 1 needs the
+                           domain of alipmpc_solve_sens_batch: fp32, the lane program, DD or N = 6 make alipmpc_create
+                           return ALIPMPC_EUNSUPPORTED; any other value ALIPMPC_EINVAL.  (The former reserved_ field:
+                           sizeof(alipmpc_cfg) is unchanged.) */
 } alipmpc_cfg;
+
+#define ALIPMPC_CL_BETWEEN_NOMINAL 0
+#define ALIPMPC_CL_BETWEEN_FIRST_ORDER 1
 
 #define ALIPMPC_GOAL_SINGULAR_ZERO 0
 #define ALIPMPC_GOAL_SINGULAR_ABORT 1
@@ -370,8 +379,30 @@ int alipmpc_closed_loop_dataset_batch(void* handle, int64_t B, int32_t S, int32_
  * launch per loop); the flow constants of every tick travel in the launch's arguments, so device-pointer calls stay
  * copy-free and allocation-free.  ALIPMPC_CL_FUSE=0 (development, read per call) launches the same kernel once per
  * nominal tick instead: the same bits.
+ *
+ * First-order ticks (a handle created with cfg.cl_between = ALIPMPC_CL_BETWEEN_FIRST_ORDER; no reference counterpart):
+ * state feedback on the MPC plan at every tick, with no further solve.  "Anchor": the last solve of the current step.
+ *   A solve tick is the solve tick above, outputs bit for bit.  When a later tick of its step does not solve it runs
+ *   as alipmpc_solve_sens_batch's launch (whose solve outputs are the solve's own bits) and keeps the anchor: xa = its
+ *   x_nex, ua = its u, du = its sensitivities; the anchor is valid iff sens_ok.  A later solve of the step replaces
+ *   the anchor; every touchdown invalidates it (leg parity and the step's constraints change there).
+ *   A non-solve tick with a valid anchor: x_nex as on a nominal tick; u_fo = ua + du[:, 0:5] (x_nex - xa) (the goal
+ *   does not move in the loop); p_0 = W (u_fo_0 - A x_nex) and x_{k+1} = M_A x_k + M_B u_fo_k as gen_control_test
+ *   derives them; and from there the tick is a solve tick whose outputs are these values: plan <- u_fo (the next
+ *   solve's warm start), nex_turn, mpc_hds_list, the close flag, the command with p_0, v_des_map from the predicted
+ *   states, the plant move, touchdown on p_0.  status_traj = ALIPMPC_TICK_FIRST_ORDER, iters_traj = 0, the plan_traj
+ *   row is u_fo.  The anchor itself does not move: every update linearises about the real solve.
+ *   A non-solve tick without one (before the step's first solve, or sens_ok = 0) is the nominal tick, as in mode 0.
+ * Held fixed by the linearisation, as by the sensitivities: obstacle selection, the detour decision and the barrier
+ * parameter.  u_fo is not checked against the constraints: plan_traj holds it for alipmpc_audit_batch.
+ * A mode-1 handle behaves as a mode-0 handle in every other entry point, and here with the all-ones mask or mask 0.
+ * Launches: after a solve left anchors, a run of non-solve ticks ends with the step and is two launches per episode
+ * group — the nominal kernel for the episodes without a valid anchor (so that their ticks have mode 0's bits) and a
+ * first-order kernel for the others; before a step's first such solve, the nominal launch alone, as in mode 0.  The
+ * anchors (B x (5 + 5N + 35N + 21) doubles) live in the handle's workspace in both pointer modes.
  */
-#define ALIPMPC_TICK_NOMINAL (-20)   /* status_traj: the tick ran the nominal ALIP law, no solve */
+#define ALIPMPC_TICK_NOMINAL (-20)       /* status_traj: the tick ran the nominal ALIP law, no solve */
+#define ALIPMPC_TICK_FIRST_ORDER (-21)   /* status_traj: the tick moved the last solve's plan to first order, no solve */
 int alipmpc_closed_loop_schedule_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc, uint64_t mpc_mask,
                                        double kick, uint64_t seed,
                                        const double* x0, const double* foot0, const double* goal, const int8_t* leg,

@@ -27,6 +27,8 @@ STATUS_NAMES = {0: "Solve_Succeeded", 1: "Solved_To_Acceptable_Level", 2: "Infea
                 -10: "Rollout_Done (goal reached earlier, not solved)"}
 ROLLOUT_DONE = -10
 TICK_NOMINAL = -20   # closed_loop_schedule: the tick ran the nominal ALIP law, no solve (ALIPMPC_TICK_NOMINAL)
+TICK_FIRST_ORDER = -21   # ... the tick moved the last solve's plan to first order (ALIPMPC_TICK_FIRST_ORDER)
+CL_BETWEEN_NOMINAL, CL_BETWEEN_FIRST_ORDER = 0, 1   # cfg.cl_between (include/alipmpc.h)
 
 _ERRORS = {-1: "EINVAL", -2: "ENODEV (no visible gfx950 device)", -3: "EHIP", -4: "EUNSUPPORTED"}
 
@@ -39,7 +41,7 @@ class Cfg(ctypes.Structure):
                 ("tol", "acceptable_tol", "dt", "H", "g", "leg2_max", "bvx_lo", "bvx_hi", "bvy_lo", "bvy_hi",
                  "dtheta_max", "q", "p", "r", "gamma", "s", "detect_r2", "dd_t", "mu_init")] + \
                [("program", ctypes.c_int32), ("goal_singular", ctypes.c_int32), ("restoration", ctypes.c_int32),
-                ("reserved_", ctypes.c_int32)]
+                ("cl_between", ctypes.c_int32)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -481,7 +483,11 @@ class Solver:
         solves the MPC if i is in mpc_ticks (an iterable of tick indices, or an int bit mask); every other tick takes
         the nominal ALIP foothold cal_foot_with_veldes(x_nex, v_des) (status TICK_NOMINAL, 0 iterations).  The default
         is the reference's hybrid driver (main_sim_mpc_alip.py: 20 ticks, one solve at tick 15).  Returns the dict of
-        closed_loop plus plan: (B, S, f_cyc, 5N) the u of every solved tick, NaN elsewhere (None unless want_plans)."""
+        closed_loop plus plan: (B, S, f_cyc, 5N) the u of every solved tick, NaN elsewhere (None unless want_plans).
+        On a handle whose cfg.cl_between is CL_BETWEEN_FIRST_ORDER, a tick between the solves of a step whose last
+        solve has valid sensitivities commands that solve's plan moved to first order with the plant instead, u_fo =
+        u + du[:, 0:5] (x_nex - x_nex of the solve): status TICK_FIRST_ORDER (-21), 0 iterations, plan row u_fo; the
+        ticks before a step's first solve, and those after a solve without valid sensitivities, stay nominal."""
         from .schedule import mask_of
         sc = dict(S=int(steps), f_cyc=int(f_cyc), mpc_mask=mask_of(mpc_ticks), kick=float(kick), seed=int(seed))
         return self._host("alipmpc_closed_loop_schedule_batch",
@@ -490,7 +496,8 @@ class Solver:
 
     def closed_loop_schedule_device(self, inp, out, steps, f_cyc=20, mpc_ticks=(15,), kick=0.0, seed=0, stream=None):
         """Asynchronous scheduled closed loop on device tensors: inp / out as closed_loop_device, out also with plan
-        (B, S, f_cyc, 5N) if the plans are wanted."""
+        (B, S, f_cyc, 5N) if the plans are wanted.  cfg.cl_between = CL_BETWEEN_FIRST_ORDER: first-order ticks (status
+        TICK_FIRST_ORDER, -21) as in closed_loop_schedule."""
         from .schedule import mask_of
         self._device("alipmpc_closed_loop_schedule_batch", inp, out, stream, inp["x0"].shape[0], int(steps), int(f_cyc),
                      mask_of(mpc_ticks), float(kick), int(seed))

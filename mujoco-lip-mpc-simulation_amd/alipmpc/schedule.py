@@ -3,21 +3,25 @@ main_sim_mpc_alip.py:71-130 on an ALIP plant.  Tick i of a step solves the MPC w
 (Logger.gen_nex_foot_input) and otherwise takes the foothold that realises the plan's desired touchdown velocity from
 the plant's projection (Logger.cal_foot_input, data_procs/logger.py:380-410: cal_foot_with_veldes(x_nex, v_des_map)).
 
-  run     drives the loop with any solver (a callable): the host restatement of the device loop
+  run     drives the loop with any solver (a callable): the host restatement of the device loop, in either mode of
+          cfg.cl_between (nominal or first-order ticks between the solves)
   replay  recomputes every step of a device loop from the device's own touchdown state x[:, s] and its recorded plans,
           so no drift crosses a step; also returns the solve inputs (x_nex, -leg_ind, u0) of every solved tick
 
 Built from the pieces of alipmpc.tsc (heading tube, command packing) and alipmpc.planner (ALIP matrices); every
 expression is written in the operation order of the device kernels (csrc/alipmpc.hip: cl_project_kernel,
-cl_update_kernel, cl_nominal_run_kernel, nominal_gait_kernel).
+cl_update_kernel, cl_nominal_run_kernel, cl_between_run_kernel / cl_first_order_plan, nominal_gait_kernel).
 """
 import math
+from fractions import Fraction
 
 import numpy as np
 
 from . import planner, tsc
 
 TICK_NOMINAL = -20     # ALIPMPC_TICK_NOMINAL
+TICK_FIRST_ORDER = -21  # ALIPMPC_TICK_FIRST_ORDER
+BETWEEN_NOMINAL, BETWEEN_FIRST_ORDER = 0, 1   # cfg.cl_between
 ROLLOUT_DONE = -10     # ALIPMPC_ROLLOUT_DONE
 VARIANT_MODI, VARIANT_SIG_STEP = 0, 1
 MAX_F_CYC = 64
@@ -97,6 +101,31 @@ def flow(x, fx, fy, hp, ch, shb, bsh, tt):
                      x[:, 4] + tt * hp], axis=1)
 
 
+def _fma(a, b, c):
+    """a * b + c rounded once, elementwise (exact rational arithmetic): the device's v_fma_f64."""
+    a, b, c = np.broadcast_arrays(np.asarray(a, np.float64), np.asarray(b, np.float64), np.asarray(c, np.float64))
+    out = np.empty(a.shape)
+    of, af, bf, cf = out.reshape(-1), a.reshape(-1), b.reshape(-1), c.reshape(-1)
+    for j in range(of.size):
+        of[j] = float(Fraction(float(af[j])) * Fraction(float(bf[j])) + Fraction(float(cf[j])))
+    return out
+
+
+def flow_device(x, fx, fy, hp, ch, shb, bsh, tt, project):
+    """flow() with the roundings of the device kernels, which contract cl_flow's expressions into fma's: position
+    fma(1 - ch, f, fma(ch, pos, shb vel)) and heading fma(tt, hp, x4) in both; velocity fma(-bsh, f, fma(bsh, pos,
+    ch vel)) in cl_project_kernel (project: a solve tick's x_nex) and fma(-f, bsh, fma(ch, vel, bsh pos)) in
+    cl_nominal_run_kernel's plant move.  (Read off the gfx950 code of the two kernels; replay's bit-exact mode.)"""
+    omc = 1.0 - ch
+    cols = []
+    for pos, vel, f in ((x[:, 0], x[:, 2], fx), (x[:, 1], x[:, 3], fy)):
+        cols.append(_fma(omc, f, _fma(ch, pos, shb * vel)))
+    for pos, vel, f in ((x[:, 0], x[:, 2], fx), (x[:, 1], x[:, 3], fy)):
+        cols.append(_fma(-bsh, f, _fma(bsh, pos, ch * vel)) if project else _fma(-f, bsh, _fma(ch, vel, pos * bsh)))
+    cols.append(_fma(tt, hp, x[:, 4]))
+    return np.stack(cols, axis=1)
+
+
 def foot_with_veldes(k, xn, vdes):
     """cal_foot_with_veldes (MPC_LIP_modi.py:188-194): B_vel^-1 (v_des - (A x)[2:4])."""
     ax = k["bsh"] * xn[:, 0] + k["ch"] * xn[:, 2]
@@ -118,6 +147,49 @@ def plan_outputs(k, xn, u):
     return foot, np.stack(xp, 1)
 
 
+def first_order_plan(k, xn, xa, ua, du):
+    """A first-order tick's plan and what follows from it (cl_first_order_plan of csrc/alipmpc.hip, its operation
+    order): u_fo = ua + du[:, :, 0:5] (x_nex - xa) (m, 5N), then p_0 (m, 3) and xk_list[1:] (m, N, 5) as plan_outputs
+    states them, every sum from 0.0 in the device's order of terms."""
+    N, m = k["N"], len(xn)
+    A, W, MA, MB = k["A"], k["W"], k["M_A"], k["M_B"]
+    xn = np.asarray(xn, float)
+    d = xn - xa
+    ua = np.asarray(ua, float).reshape(m, N, 5)
+    du = np.asarray(du, float).reshape(m, N, 5, -1)
+    u = np.empty((m, N, 5))
+    for kk in range(N):
+        for c in range(5):
+            v = np.zeros(m)
+            for j in range(5):
+                v = v + du[:, kk, c, j] * d[:, j]
+            u[:, kk, c] = ua[:, kk, c] + v
+    e = np.empty((m, 5))
+    for i in range(5):
+        v = np.zeros(m)
+        for c in range(5):
+            v = v + A[i, c] * xn[:, c]
+        e[:, i] = u[:, 0, i] - v
+    foot = np.empty((m, 3))
+    for i in range(3):
+        v = np.zeros(m)
+        for c in range(5):
+            v = v + W[i, c] * e[:, c]
+        foot[:, i] = v
+    xk, xp = xn, np.empty((m, N, 5))
+    for kk in range(N):
+        y = np.empty((m, 5))
+        for i in range(5):
+            v = np.zeros(m)
+            for c in range(5):
+                v = v + MA[i, c] * xk[:, c]
+            for c in range(5):
+                v = v + MB[i, c] * u[:, kk, c]
+            y[:, i] = v
+        xk = xp[:, kk] = y
+    return u.reshape(m, 5 * N), foot, xp
+
+
 def _rot(th, vx, vy):
     c, s = np.cos(th), np.sin(th)
     return c * vx + s * vy, -s * vx + c * vy
@@ -137,7 +209,13 @@ def command(p0, foot, fx, fy, xn, vdes, hd, hp, hcos, i, F):
     return tsc.gen_tsc_control(fi, npf, nvf, hp, hcos - p0[:, 2], i, F)
 
 
-def _loop(cfg, inp, mask, steps, f_cyc, kick, seed, solve, dev):
+def _close(variant, xp, goal):
+    """close_2_goal of a plan's predicted states xp (m, N, 5)."""
+    d = np.sqrt(((xp[:, :, 0:2] - goal[:, None, :]) ** 2).sum(-1))
+    return (d <= 0.35).any(1) if variant == VARIANT_SIG_STEP else d[:, 0] <= 0.15
+
+
+def _loop(cfg, inp, mask, steps, f_cyc, kick, seed, solve, dev, between=BETWEEN_NOMINAL, sens=None):
     k = constants(cfg)
     N, n, variant = k["N"], 5 * k["N"], k["variant"]
     S, F = int(steps), int(f_cyc)
@@ -170,10 +248,20 @@ def _loop(cfg, inp, mask, steps, f_cyc, kick, seed, solve, dev):
     iters = np.zeros((B, S, F), np.int32)
     stg = np.full(B, -1, np.int32)
     solves = dict(b=[], s=[], i=[], x_nex=[], leg=[], u0=[])
+    # first-order mode: the anchor of every episode (the last solve of the current step: its x_nex, plan, du[:, :, 0:5]
+    # and tick), valid where that solve's sens_ok is set and no touchdown came since
+    fo_mode = int(between) == BETWEEN_FIRST_ORDER
+    exact = dev is not None and dev.get("hd") is not None and dev.get("foot") is not None
+    a_x, a_u, a_du = np.zeros((B, 5)), np.zeros((B, n)), np.zeros((B, n, 5))
+    a_ok, a_i = np.zeros(B, bool), np.full(B, -1)
+    fos = dict(b=[], s=[], i=[], x_nex=[], anchor_i=[])
+    anchors = dict(b=[], s=[], i=[], sens_ok=[], du=[])
     for s in range(S):
         if dev is not None:   # replay: every step from the device's own touchdown state and its set of episodes
             x = np.array(dev["x"][:, s], np.float64)
             active = np.asarray(dev["status"])[:, s, 0] != ROLLOUT_DONE
+            if exact and s > 0:   # and from its own stance foot
+                pst[active] = dev["foot"][active, s - 1, 0:2]
         for i in range(F):
             idx = np.nonzero(active)[0]
             if len(idx) == 0:
@@ -190,10 +278,13 @@ def _loop(cfg, inp, mask, steps, f_cyc, kick, seed, solve, dev):
                 for j in range(3):
                     ssum = ssum + tsc.angle_a_minus_b(mhd[idx, j], prev[j])
                 hd_pr[idx] = ssum / 4.0
+                if exact:   # the device's own heading inputs
+                    hd_pr[idx], hd_cos[idx] = dev["hd"][idx, s, 0], dev["hd"][idx, s, 1]
                 hd[idx, s, 0], hd[idx, s, 1] = hd_pr[idx], hd_cos[idx]
             xi, fx, fy, hp = x[idx], pst[idx, 0], pst[idx, 1], hd_pr[idx]
-            xn = flow(xi, fx, fy, hp, ch_r, shb_r, bsh_r, tr)
             solved = bool(mask >> i & 1)
+            xn = (flow_device(xi, fx, fy, hp, ch_r, shb_r, bsh_r, tr, True) if exact and solved else
+                  flow(xi, fx, fy, hp, ch_r, shb_r, bsh_r, tr))
             if solved:
                 u0 = np.tile(xn, (1, N))
                 hp_ = has_plan[idx]
@@ -213,6 +304,19 @@ def _loop(cfg, inp, mask, steps, f_cyc, kick, seed, solve, dev):
                         solves[key].append(v)
                 else:
                     o = solve(xn, od, u0, idx)
+                if fo_mode:   # a later tick of the step does not solve: this solve leaves the anchor
+                    if (all_ones(F) & ~mask) >> (i + 1):
+                        du_, ok_ = sens(xn, od, u0, idx) if dev is not None else (o["du"], o["sens_ok"])
+                        ok_ = np.asarray(ok_).reshape(len(idx)) != 0
+                        du_ = np.asarray(du_, np.float64).reshape(len(idx), n, -1)
+                        a_ok[idx] = ok_
+                        j = idx[ok_]
+                        a_x[j], a_u[j], a_du[j], a_i[j] = xn[ok_], np.asarray(o["u"])[ok_], du_[ok_][:, :, 0:5], i
+                        for key, v in (("b", idx), ("s", np.full(len(idx), s)), ("i", np.full(len(idx), i)),
+                                       ("sens_ok", ok_), ("du", du_)):
+                            anchors[key].append(v)
+                    else:
+                        a_ok[idx] = False
                 status[idx, s, i] = o["status"]
                 iters[idx, s, i] = o["iters"]
                 plan[idx] = o["u"]
@@ -221,23 +325,43 @@ def _loop(cfg, inp, mask, steps, f_cyc, kick, seed, solve, dev):
                 nex_turn[idx] = o["foot"][:, 2]
                 xp = np.asarray(o["x_pred"]).reshape(len(idx), N, 5)
                 mhd[idx, :min(3, N)] = xp[:, :3, 4]
-                d = np.sqrt(((xp[:, :, 0:2] - goal[idx, None, :]) ** 2).sum(-1))
-                close = (d <= 0.35).any(1) if variant == VARIANT_SIG_STEP else d[:, 0] <= 0.15
+                close = _close(variant, xp, goal[idx])
                 nfoot = np.asarray(o["foot"])[:, 0:2]
+                fo = np.zeros(len(idx), bool)
             else:
                 nfoot = foot_with_veldes(k, xn, vdes[idx])
                 status[idx, s, i] = TICK_NOMINAL
                 iters[idx, s, i] = 0
+                # first-order ticks: the episodes with a valid anchor (replay: the ticks the device ran as such)
+                fo = np.zeros(len(idx), bool)
+                if fo_mode:
+                    fo = np.asarray(dev["status"])[idx, s, i] == TICK_FIRST_ORDER if dev is not None else a_ok[idx]
+                if fo.any():   # a solve tick whose outputs follow from u_fo
+                    j = idx[fo]
+                    u_fo, ft, xp = first_order_plan(k, xn[fo], a_x[j], a_u[j], a_du[j])
+                    status[j, s, i] = TICK_FIRST_ORDER
+                    # (bit-exact replay: the next solve's warm start is the device's row, the replay's own is returned)
+                    plan[j] = np.asarray(dev["plan"])[j, s, i] if exact else u_fo
+                    plans[j, s, i] = u_fo
+                    nex_turn[j] = ft[:, 2]
+                    mhd[j, :min(3, N)] = xp[:, :3, 4]
+                    close = _close(variant, xp, goal[j])
+                    nfoot[fo] = ft[:, 0:2]
+                    for key, v in (("b", j), ("s", np.full(len(j), s)), ("i", np.full(len(j), i)), ("x_nex", xn[fo]),
+                                   ("anchor_i", a_i[j])):
+                        fos[key].append(v)
             target[idx, s, i] = nfoot
             action[idx, s, i] = command(pose0[idx], nfoot, fx, fy, xn, vdes[idx], xi[:, 4], hp, hd_cos[idx], i, F)
-            if solved:   # vel_des <- mpc_state_tar[0][2:4] after a solve, [1][2:4] at touchdown
+            if solved or fo.any():   # vel_des <- mpc_state_tar[0][2:4] after a solve, [1][2:4] at touchdown
                 kv = 1 if (i == F - 1 and N > 1) else 0
-                vdes[idx] = xp[:, kv, 2:4]
-            xa = flow(xi, fx, fy, hp, ch_d, shb_d, bsh_d, td)
+                vdes[idx[fo] if not solved else idx] = xp[:, kv, 2:4]
+            nominal_move = exact and not solved and not fo.any()   # (the move of cl_nominal_run_kernel, to the bit)
+            xa = (flow_device(xi, fx, fy, hp, ch_d, shb_d, bsh_d, td, False) if nominal_move else
+                  flow(xi, fx, fy, hp, ch_d, shb_d, bsh_d, td))
             if kick > 0:
-                for j, b in enumerate(idx):
-                    xa[j, 2] += kick * (2.0 * cl_uniform(seed, int(b), s, i, 0) - 1.0)
-                    xa[j, 3] += kick * (2.0 * cl_uniform(seed, int(b), s, i, 1) - 1.0)
+                for ax in (0, 1):
+                    kv_ = np.array([2.0 * cl_uniform(seed, int(b), s, i, ax) - 1.0 for b in idx])
+                    xa[:, 2 + ax] = _fma(kick, kv_, xa[:, 2 + ax]) if nominal_move else xa[:, 2 + ax] + kick * kv_
             x[idx] = xa
             if i == F - 1:   # touchdown
                 pst[idx] = nfoot
@@ -246,12 +370,16 @@ def _loop(cfg, inp, mask, steps, f_cyc, kick, seed, solve, dev):
                 foot[idx, s, 2] = nex_turn[idx]
                 if not solved:
                     pl = plan[idx].reshape(len(idx), N, 5)[:, 1 if N > 1 else 0, 2:4]
-                    vdes[idx] = np.where(has_plan[idx, None], pl, des_vel(k, leg[idx]))
+                    nominal = np.where(has_plan[idx, None], pl, des_vel(k, leg[idx]))
+                    vdes[idx] = np.where(fo[:, None], vdes[idx], nominal)   # (a first-order tick took its own)
                 stop = idx[rclose[idx]]
                 active[stop] = False
                 stg[stop] = s + 1
+                a_ok[idx] = False   # the linearisation does not carry over a touchdown
             if solved:
                 rclose[idx] |= close
+            elif fo.any():
+                rclose[idx[fo]] |= close
         xs[:, s + 1] = x
     out = dict(foot=foot, x=xs, hd=hd, status=status, iters=iters, steps_to_goal=stg, action=action, plan=plans,
                target=target)
@@ -260,27 +388,59 @@ def _loop(cfg, inp, mask, steps, f_cyc, kick, seed, solve, dev):
         out["solves"] = dict(b=cat(solves["b"], (0,)).astype(np.int64), s=cat(solves["s"], (0,)).astype(np.int64),
                              i=cat(solves["i"], (0,)).astype(np.int64), x_nex=cat(solves["x_nex"], (0, 5)),
                              leg=cat(solves["leg"], (0,)).astype(np.int8), u0=cat(solves["u0"], (0, n)))
+        if fo_mode:
+            ci = lambda v: cat(v, (0,)).astype(np.int64)   # noqa: E731
+            out["fo"] = dict(b=ci(fos["b"]), s=ci(fos["s"]), i=ci(fos["i"]), x_nex=cat(fos["x_nex"], (0, 5)),
+                             anchor_i=ci(fos["anchor_i"]))
+            out["anchors"] = dict(b=ci(anchors["b"]), s=ci(anchors["s"]), i=ci(anchors["i"]),
+                                  sens_ok=cat(anchors["sens_ok"], (0,)).astype(bool),
+                                  du=cat(anchors["du"], (0, n, 7)))
     return out
 
 
-def run(cfg, inputs, mask, solve=None, steps=8, f_cyc=20, kick=0.0, seed=0):
+def _between(cfg, between):
+    b = int(getattr(cfg, "cl_between", BETWEEN_NOMINAL) if between is None else between)
+    if b not in (BETWEEN_NOMINAL, BETWEEN_FIRST_ORDER):
+        raise ValueError(f"between = {b}")
+    return b
+
+
+def run(cfg, inputs, mask, solve=None, steps=8, f_cyc=20, kick=0.0, seed=0, between=None):
     """The scheduled loop on the host.  cfg: an object with N, variant, dt, g, H (a Cfg); inputs: dict with x0 (B, 5),
     foot0 (B, 2), goal, leg; mask: int mask or iterable of solved ticks; solve(x_nex (n, 5), od_ev (n,), u0 (n, 5N),
-    idx (n,) the episodes) -> dict(u, foot, x_pred, status, iters) — not needed for mask 0.  Returns the dict of
-    Solver.closed_loop_schedule (plan included, NaN rows on nominal ticks and after the stop) plus target (B, S, f_cyc,
-    2): the foothold every tick commands."""
+    idx (n,) the episodes) -> dict(u, foot, x_pred, status, iters) — not needed for mask 0.  between: what a tick
+    without a solve does, BETWEEN_NOMINAL or BETWEEN_FIRST_ORDER (None: cfg.cl_between, 0 where cfg has none); in
+    first-order mode solve's dict also carries du (n, 5N, 7) and sens_ok (n,) (Solver.solve_sens's), and a tick with a
+    valid anchor moves the anchor's plan by du[:, :, 0:5] (x_nex - x_nex of the anchor) (status TICK_FIRST_ORDER).
+    Returns the dict of Solver.closed_loop_schedule (plan included, NaN rows on nominal ticks and after the stop) plus
+    target (B, S, f_cyc, 2): the foothold every tick commands."""
     if solve is None and mask_of(mask, f_cyc):
         raise ValueError("a schedule with solved ticks needs a solve callable")
-    return _loop(cfg, inputs, mask, steps, f_cyc, float(kick), int(seed), solve, None)
+    return _loop(cfg, inputs, mask, steps, f_cyc, float(kick), int(seed), solve, None, _between(cfg, between))
 
 
-def replay(cfg, inputs, mask, x_traj, plan_traj, status_traj, kick=0.0, seed=0):
+def replay(cfg, inputs, mask, x_traj, plan_traj, status_traj, kick=0.0, seed=0, sens=None, foot_traj=None,
+           hd_traj=None):
     """Every step of a device loop recomputed from the device's own touchdown state x_traj[:, s], the episodes it
     still ran (status_traj[:, s, 0]) and the plans it recorded (plan_traj), a solve's foothold and predicted states
     derived from its plan as gen_control_test does (plan_outputs).  Returns foot, hd, x (x[:, s + 1] from
     x_traj[:, s]), action — the values to hold against the device's — and solves: dict(b, s, i, x_nex, leg, u0), the
-    inputs of every solved tick.  (iters is not replayed; steps_to_goal follows from status.)"""
+    inputs of every solved tick.  (iters is not replayed; steps_to_goal follows from status.)
+    A first-order loop (a handle with cfg.cl_between = 1) is replayed when sens is given: sens(x_nex, od_ev, u0, idx)
+    -> (du (n, 5N, 7), sens_ok (n,)) is called at every replayed solve tick that leaves an anchor; the ticks the device
+    recorded as TICK_FIRST_ORDER are recomputed from the anchor (their plan rows are the replay's own, not the
+    device's), and the result also holds fo: dict(b, s, i, x_nex, anchor_i), the first-order ticks, and anchors:
+    dict(b, s, i, sens_ok, du), the solves that left (or failed to leave) an anchor.
+    Bit-exact solve inputs: with the device's foot_traj and hd_traj also given, every step restarts from the device's
+    stance foot and heading inputs as well, the plant moves of the nominal ticks and the projection of a solve tick
+    round as the device kernels do (flow_device), and the warm start after a first-order tick is the device's recorded
+    row — so that up to a step's first solve x_nex and u0 are the device's own bits, and a solve of them on the same
+    handle is the device's solve.  (A step in which a nominal tick follows a solve or first-order tick is exact up to
+    that solve only; the other outputs are compared within a tolerance either way.)"""
     st = np.asarray(status_traj)
     B, S, F = st.shape
-    dev = dict(x=np.asarray(x_traj, np.float64), plan=np.asarray(plan_traj, np.float64).reshape(B, S, F, -1), status=st)
-    return _loop(cfg, inputs, mask, S, F, float(kick), int(seed), None, dev)
+    dev = dict(x=np.asarray(x_traj, np.float64), plan=np.asarray(plan_traj, np.float64).reshape(B, S, F, -1), status=st,
+               foot=None if foot_traj is None else np.asarray(foot_traj, np.float64),
+               hd=None if hd_traj is None else np.asarray(hd_traj, np.float64))
+    return _loop(cfg, inputs, mask, S, F, float(kick), int(seed), None, dev,
+                 BETWEEN_NOMINAL if sens is None else BETWEEN_FIRST_ORDER, sens)

@@ -2944,7 +2944,9 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK, (solve_waves<KSM, double, R
     for (long long b = next_instance(q); b < Pv.B; b = next_instance(q)) {
         long long rec = -1;
         asm volatile("" : "+s"(rec));
-        solve_one<N, KSM, double, true, false, RS, false, true>(P, G, wsb, wv, b, rec);
+        // (the scheduled closed loop's first-order mode: skip finished episodes, as solve_kernel's work queue does; no
+        // launch order here)
+        if (!Pv.active || Pv.active[b]) solve_one<N, KSM, double, true, false, RS, false, true>(P, G, wsb, wv, b, rec);
     }
     queue_exit(q);
 }
@@ -5081,11 +5083,13 @@ __global__ __launch_bounds__(256) void nominal_gait_kernel(NgP Q)
 // episode's state is loaded once, kept in registers over the run and stored once; the outputs of every tick are
 // written as the per-tick kernels write them.  The flow constants of each tick index travel by value.
 // ------------------------------------------------------------------------------------------------
+constexpr uint8_t CL_FLAG_ANCHOR = 8;   // CLP::flags bit 3, first-order mode: the episode has a valid anchor (below)
 constexpr int CL_MAX_F = 64;   // f_cyc of a scheduled loop: a bit of the mask and a row of CLN::rest per tick
 struct CLN {
     CLP C;                    // the episode group's arguments (its s, i and rest-flow constants are not read)
     long long t0;             // first tick of the run, s * f + i
     int nt;                   // ticks of the run, t0 + nt <= S * f
+    int skip_anchored;        // first-order mode: leave the episodes with the anchor bit to cl_between_run_kernel
     double bsh, ch, ibv;      // cal_foot_with_veldes: beta sinh(beta T), cosh(beta T), 1 / (-beta sinh(beta T))
     double* plan_traj;        // B x S x f x 5N or NULL: NaN rows on these ticks
     double rest[CL_MAX_F][4]; // per tick index: cosh, sinh / beta, beta sinh of rest_t, rest_t / T
@@ -5097,6 +5101,7 @@ __global__ __launch_bounds__(256) void cl_nominal_run_kernel(CLN Q)
     const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= C.B) return;
     uint8_t fl = C.flags[b];
+    if (Q.skip_anchored && (fl & CL_FLAG_ANCHOR)) return;   // (first-order mode: cl_between_run_kernel's episodes)
     double x[5], hv[3], mh[3], p0[3];
     for (int c = 0; c < 5; ++c) x[c] = C.x[5 * b + c];
     for (int c = 0; c < 3; ++c) {
@@ -5174,6 +5179,190 @@ __global__ __launch_bounds__(256) void cl_nominal_run_kernel(CLN Q)
     }
     for (int c = 0; c < 5; ++c) C.x[5 * b + c] = x[c];
     for (int c = 0; c < 3; ++c) C.hdv[4 * b + c] = hv[c];
+    C.pst[2 * b] = fx;
+    C.pst[2 * b + 1] = fy;
+    C.vdes[2 * b] = vd[0];
+    C.vdes[2 * b + 1] = vd[1];
+    C.leg[b] = (int8_t)leg;
+    C.flags[b] = fl;
+}
+
+// ------------------------------------------------------------------------------------------------
+// first-order ticks (cfg.cl_between = ALIPMPC_CL_BETWEEN_FIRST_ORDER): between the solves of a step the last solve's
+// plan follows the plant to first order, u_fo = ua + du[:, 0:5] (x_nex - xa), about the anchor (xa, ua, du) that
+// solve left (its x_nex, its u and alipmpc_solve_sens_batch's du; the goal columns are not read: the
+// goal does not move in the loop).  Bit 3 of CLP::flags says that the episode has a valid anchor: set by
+// cl_anchor_kernel after a solve tick whose sensitivities are valid, cleared by a later solve of the step without
+// them and at every touchdown.  A non-solve tick with the bit set is a solve tick whose outputs are (u_fo, and the
+// foothold and predicted states gen_control_test derives from it: cl_first_order_plan); without it, the nominal tick.
+// ------------------------------------------------------------------------------------------------
+struct CLB {
+    CLN Q;
+    const double* xa;   // B x 5: x_nex of the anchor solve
+    const double* ua;   // B x 5N: its plan
+    const double* du;   // B x 5N x 7: its sensitivities (columns 0..4: x0)
+    double A[25], W[15], MA[25], MB[25];   // the step map (AlipMats), row-major
+};
+static_assert(sizeof(CLB) <= 4096, "kernel arguments of cl_between_run_kernel");
+
+// The plan of a first-order tick and what cl_update_kernel takes from a solve's outputs, row by row (N is a run-time
+// value: no array of 5N lives in registers): u_fo into plan (and row, the plan_traj row, if not NULL);
+// foot = p_0 = W (u_0 - A x_nex); x_{k+1} = M_A x_k + M_B u_k (trace_kernel's expressions), of which mh takes the
+// headings of the first three, nvd the velocity of state kv, and the return value is close_2_goal.
+__device__ inline bool cl_first_order_plan(const CLB& F, int N, int variant, int kv, const double* goal,
+                                           const double* xn, const double* xa, const double* ua, const double* du,
+                                           double* plan, double* row, double* foot, double* mh, double* nvd)
+{
+    double d[5], xk[5];
+    for (int c = 0; c < 5; ++c) {
+        d[c] = xn[c] - xa[c];
+        xk[c] = xn[c];
+    }
+    const int kmax = variant == ALIPMPC_VARIANT_SIG_STEP ? N : 1;
+    const double rad = variant == ALIPMPC_VARIANT_MODI ? 0.15 : 0.35;
+    bool close = false;
+    for (int k = 0; k < N; ++k) {
+        double uk[5];
+        for (int c = 0; c < 5; ++c) {
+            const double* r = du + (size_t)(5 * k + c) * 7;
+            double v = 0.0;
+            for (int j = 0; j < 5; ++j) v += r[j] * d[j];
+            uk[c] = ua[5 * k + c] + v;
+        }
+        if (k == 0) {
+            double e[5];
+            for (int i = 0; i < 5; ++i) {
+                double v = 0.0;
+                for (int c = 0; c < 5; ++c) v += F.A[i * 5 + c] * xn[c];
+                e[i] = uk[i] - v;
+            }
+            for (int i = 0; i < 3; ++i) {
+                double v = 0.0;
+                for (int c = 0; c < 5; ++c) v += F.W[i * 5 + c] * e[c];
+                foot[i] = v;
+            }
+        }
+        double y[5];
+        for (int i = 0; i < 5; ++i) {
+            double v = 0.0;
+            for (int c = 0; c < 5; ++c) v += F.MA[i * 5 + c] * xk[c];
+            for (int c = 0; c < 5; ++c) v += F.MB[i * 5 + c] * uk[c];
+            y[i] = v;
+        }
+        for (int c = 0; c < 5; ++c) {
+            xk[c] = y[c];
+            plan[5 * k + c] = uk[c];
+            if (row) row[5 * k + c] = uk[c];
+        }
+        if (k == 0) mh[0] = xk[4];
+        else if (k == 1) mh[1] = xk[4];
+        else if (k == 2) mh[2] = xk[4];
+        if (k == kv) {
+            nvd[0] = xk[2];
+            nvd[1] = xk[3];
+        }
+        if (k < kmax) {
+            const double dx = xk[0] - goal[0], dy = xk[1] - goal[1];
+            close = close || sqrt(dx * dx + dy * dy) <= rad;
+        }
+    }
+    return close;
+}
+
+// anchor of a mode-1 solve tick (after cl_update_kernel).  have: the tick ran the sensitivity build (a later tick of
+// the step does not solve), which wrote du itself: xa, ua <- this tick's x_nex and u, the anchor bit <- sens_ok.
+// Otherwise the bit is cleared (no tick reads it before the touchdown clears it anyway).
+struct CLA {
+    long long B;
+    int n, have;
+    const uint8_t* active;   // the solve's active mask (cl_project_kernel)
+    uint8_t* flags;
+    const double *xs, *u;
+    const int32_t* ok;
+    double *xa, *ua;
+};
+__global__ __launch_bounds__(256) void cl_anchor_kernel(CLA Q)
+{
+    const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= Q.B || !Q.active[b]) return;
+    uint8_t fl = Q.flags[b] & (uint8_t)~CL_FLAG_ANCHOR;
+    if (Q.have && Q.ok[b] != 0) {
+        for (int c = 0; c < 5; ++c) Q.xa[5 * b + c] = Q.xs[5 * b + c];
+        for (int c = 0; c < Q.n; ++c) Q.ua[(size_t)b * Q.n + c] = Q.u[(size_t)b * Q.n + c];
+        fl |= CL_FLAG_ANCHOR;
+    }
+    Q.flags[b] = fl;
+}
+
+// The first-order ticks of a run of non-solve ticks inside one step, for the episodes whose anchor bit is set (the
+// others run cl_nominal_run_kernel, which skips these: a nominal tick is computed by one kernel, mode 0's, so that it
+// has mode 0's bits).  The bit changes only at a solve tick or a touchdown, i.e. at the ends of such a run, so every
+// tick here is first-order: x_nex as the nominal tick has it, cl_first_order_plan, then cl_update_kernel's sequence
+// with the state in registers, as cl_nominal_run_kernel keeps it.  (Tick 0 of a step never comes here: the bit is
+// set by a solve of the step.)  The anchor rows are read where a tick uses them: 840 B per episode and tick at N = 3,
+// from the caches after the first.
+__global__ __launch_bounds__(256) void cl_between_run_kernel(CLB F)
+{
+    const CLN& Q = F.Q;
+    const CLP& C = Q.C;
+    const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= C.B) return;
+    uint8_t fl = C.flags[b];
+    if (!(fl & 1) || !(fl & CL_FLAG_ANCHOR)) return;
+    double x[5], hv[3], mh[3], p0[3];
+    for (int c = 0; c < 5; ++c) x[c] = C.x[5 * b + c];
+    for (int c = 0; c < 3; ++c) {
+        hv[c] = C.hdv[4 * b + c];
+        mh[c] = C.mhd[3 * b + c];
+        p0[c] = C.pose0[3 * b + c];
+    }
+    double fx = C.pst[2 * b], fy = C.pst[2 * b + 1], vd[2] = {C.vdes[2 * b], C.vdes[2 * b + 1]};
+    int leg = C.leg[b];
+    const int n = 5 * C.N;
+    const int s = (int)(Q.t0 / C.f);
+    int i = (int)(Q.t0 - (long long)s * C.f);
+    const size_t si = (size_t)b * C.S + s;
+    for (int t = 0; t < Q.nt; ++t, ++i) {   // (host: the run stays inside step s)
+        const size_t ti = si * C.f + i;
+        if (C.status_traj) C.status_traj[ti] = ALIPMPC_TICK_FIRST_ORDER;
+        if (C.iters_traj) C.iters_traj[ti] = 0;
+        const double* r = Q.rest[i];
+        double xn[5], ft[3], nvd[2] = {0.0, 0.0};
+        cl_flow(x, fx, fy, hv[1], r[0], r[1], r[2], r[3], xn);
+        const bool close = cl_first_order_plan(F, C.N, C.variant, (i == C.f - 1 && C.N > 1) ? 1 : 0, C.goal + 2 * b, xn,
+                                               F.xa + 5 * b, F.ua + (size_t)b * n, F.du + (size_t)b * n * 7,
+                                               C.plan + (size_t)b * n, Q.plan_traj ? Q.plan_traj + ti * n : nullptr,
+                                               ft, mh, nvd);
+        hv[0] = ft[2];   // nex_turn
+        // the command of this tick's plan: p_0, x_nex and v_des_map before this tick's update
+        if (C.action_traj) cl_command(p0, ft, fx, fy, xn, vd, x, hv, C.f, i, C.action_traj + ti * 8);
+        vd[0] = nvd[0];
+        vd[1] = nvd[1];
+        double xa[5];
+        cl_flow(x, fx, fy, hv[1], C.ch_d, C.shb_d, C.bsh_d, C.td, xa);
+        cl_kick(C.kick, C.seed, C.b0 + b, s, i, xa);
+        for (int c = 0; c < 5; ++c) x[c] = xa[c];
+        if (i == C.f - 1) {   // touchdown on p_0; the linearisation does not carry over
+            fx = ft[0];
+            fy = ft[1];
+            leg = -leg;
+            if (C.foot_traj)
+                for (int c = 0; c < 3; ++c) C.foot_traj[si * 3 + c] = ft[c];
+            if (C.x_traj)
+                for (int c = 0; c < 5; ++c) C.x_traj[((size_t)b * (C.S + 1) + s + 1) * 5 + c] = x[c];
+            if (fl & 4) {
+                fl &= (uint8_t)~1u;
+                if (C.steps_to_goal) C.steps_to_goal[b] = s + 1;
+            }
+            fl &= (uint8_t)~CL_FLAG_ANCHOR;
+        }
+        if (close) fl |= 4;
+    }
+    for (int c = 0; c < 5; ++c) C.x[5 * b + c] = x[c];
+    for (int c = 0; c < 3; ++c) {
+        C.hdv[4 * b + c] = hv[c];
+        C.mhd[3 * b + c] = mh[c];
+    }
     C.pst[2 * b] = fx;
     C.pst[2 * b + 1] = fy;
     C.vdes[2 * b] = vd[0];

@@ -798,6 +798,13 @@ int alipmpc_create(const alipmpc_cfg* cfg, int device, void** handle)
     if (cfg->variant != ALIPMPC_VARIANT_MODI && cfg->variant != ALIPMPC_VARIANT_SIG_STEP &&
         cfg->variant != ALIPMPC_VARIANT_DD)
         return ALIPMPC_EINVAL;
+    if (cfg->cl_between != ALIPMPC_CL_BETWEEN_NOMINAL && cfg->cl_between != ALIPMPC_CL_BETWEEN_FIRST_ORDER)
+        return ALIPMPC_EINVAL;
+    // first-order ticks read the sensitivity build's du: alipmpc_solve_sens_batch's domain
+    if (cfg->cl_between == ALIPMPC_CL_BETWEEN_FIRST_ORDER &&
+        (cfg->variant == ALIPMPC_VARIANT_DD || cfg->precision == ALIPMPC_PREC_FP32 ||
+         cfg->program == ALIPMPC_PROGRAM_LANE || cfg->N > 5))
+        return ALIPMPC_EUNSUPPORTED;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return ALIPMPC_ENODEV;
     hipDeviceProp_t prop;
@@ -1082,6 +1089,21 @@ int alipmpc_solve_batch(void* handle, int64_t B, const double* x0, const double*
                      iters, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, hip_stream);
 }
 
+// the sensitivity build's launch of a handle in its domain (fp64 wave program, N <= 5); P carries dfoot, du and sens_ok
+// in grad_out, J_out and active_out
+static hipError_t launch_sens(Handle* h, const KP& P, hipStream_t st)
+{
+    const size_t smem = smem_bytes(h, true);
+    switch (h->N) {
+    case 1: return launch_sens_1(P, smem, st);
+    case 2: return launch_sens_2(P, smem, st);
+    case 3: return launch_sens_3(P, smem, st);
+    case 4: return launch_sens_4(P, smem, st);
+    case 5: return launch_sens_5(P, smem, st);
+    }
+    return hipErrorInvalidValue;
+}
+
 // The solve with its sensitivities (DESIGN.md §3.7): one launch of the sensitivity build's work queue.  Its three
 // outputs reach the kernel in KP's eval-output slots (sens_wave.inc: sens_dfoot, sens_du, sens_okp), which a solve
 // launch leaves unused.
@@ -1126,16 +1148,7 @@ int alipmpc_solve_sens_batch(void* handle, int64_t B, const double* x0, const do
     P.active_out = reinterpret_cast<int8_t*>(d_ok);
     TimedSpan span{h, S.st};
     if (int e = span.begin()) return e;
-    const size_t smem = smem_bytes(h, true);
-    hipError_t le = hipErrorInvalidValue;
-    switch (N) {
-    case 1: le = launch_sens_1(P, smem, S.st); break;
-    case 2: le = launch_sens_2(P, smem, S.st); break;
-    case 3: le = launch_sens_3(P, smem, S.st); break;
-    case 4: le = launch_sens_4(P, smem, S.st); break;
-    case 5: le = launch_sens_5(P, smem, S.st); break;
-    }
-    HIPCHK(h, le);
+    HIPCHK(h, launch_sens(h, P, S.st));
     if (int e = span.end()) return e;
     return S.finish();
 }
@@ -1327,6 +1340,17 @@ static int closed_loop_impl(Handle* h, int64_t B, int32_t S, int32_t f_cyc, doub
             Z.out_area(D.row_status, ds->row_status, ds_cap);
         }
     }
+    // first-order ticks (cfg.cl_between, a scheduled loop only): each episode's anchor, and the other two outputs of
+    // the sensitivity build (a host-pointer schedule registers 32 slots, + 5: within Staging::MAX_SLOTS)
+    const bool fo_mode = sch && cf.cl_between == ALIPMPC_CL_BETWEEN_FIRST_ORDER;
+    struct {
+        double *xa, *ua, *du, *dfoot;
+        int32_t* ok;
+    } an{};
+    if (fo_mode) {
+        Z.work(an.xa, Bz * 5); Z.work(an.ua, Bz * n); Z.work(an.du, Bz * n * 7); Z.work(an.dfoot, Bz * 21);
+        Z.work(an.ok, Bz);
+    }
     if (int e = Z.commit()) {
         if (Z.alloc_err == hipSuccess) return e;
         (void)hipGetLastError();
@@ -1369,6 +1393,8 @@ static int closed_loop_impl(Handle* h, int64_t B, int32_t S, int32_t f_cyc, doub
         hipStream_t s;
         unsigned g1;
         double* plan_traj;
+        double *xa, *ua, *du, *dfoot;   // first-order mode: the group's anchors and sensitivity outputs
+        int32_t* ok;
     } grp[Handle::MAXG];
     const long long nn = n, SF = (long long)S * f_cyc;
     for (int g = 0; g < G; ++g) {
@@ -1394,6 +1420,8 @@ static int closed_loop_impl(Handle* h, int64_t B, int32_t S, int32_t f_cyc, doub
         grp[g].P = q;
         grp[g].g1 = (unsigned)((Bg + 255) / 256);
         grp[g].plan_traj = d_plan ? d_plan + b0 * SF * nn : nullptr;
+        grp[g].xa = an.xa; grp[g].ua = an.ua; grp[g].du = an.du; grp[g].dfoot = an.dfoot; grp[g].ok = an.ok;
+        o(grp[g].xa, 5); o(grp[g].ua, nn); o(grp[g].du, 7 * nn); o(grp[g].dfoot, 21); o(grp[g].ok, 1);
         grp[g].s = st;
         if (G > 1) {
             if (!h->gst[g]) HIPCHK(h, hipStreamCreateWithFlags(&h->gst[g], hipStreamNonBlocking));
@@ -1424,20 +1452,47 @@ static int closed_loop_impl(Handle* h, int64_t B, int32_t S, int32_t f_cyc, doub
         const char* fe = std::getenv("ALIPMPC_CL_FUSE");
         fuse = !(fe && std::strcmp(fe, "0") == 0);
     }
+    CLB Qb;   // first-order mode: cl_between_run_kernel's arguments, a run's CLN and the step map of cl_first_order_plan
+    if (fo_mode) {
+        std::memset(&Qb, 0, sizeof(Qb));
+        std::memcpy(Qb.A, am.A, sizeof(Qb.A));
+        std::memcpy(Qb.W, am.W, sizeof(Qb.W));
+        std::memcpy(Qb.MA, am.MA, sizeof(Qb.MA));
+        std::memcpy(Qb.MB, am.MB, sizeof(Qb.MB));
+    }
     auto solves = [&](int i) { return !sch || ((sch->mask >> i) & 1ull) != 0; };
+    // first-order mode: does a tick of the step after tick i not solve (then tick i's solve leaves an anchor)
+    auto anchors = [&](int i) {
+        for (int j = i + 1; j < f_cyc; ++j)
+            if (!solves(j)) return true;
+        return false;
+    };
+    int live_step = -1;   // first-order mode: the step in which a solve tick last left anchors
     const long long TT = (long long)S * f_cyc;
     for (long long t = 0; t < TT;) {
         const int s = (int)(t / f_cyc), i = (int)(t % f_cyc);
         if (!solves(i)) {   // a run of nominal ticks, possibly across step boundaries: one launch per group
+            // First-order mode, after a solve of this step left anchors: the run ends with the step (the anchor bits
+            // change there), its anchored episodes run cl_between_run_kernel and cl_nominal_run_kernel skips them.
+            // Before a step's first anchor no bit is set: the nominal launch alone, as in mode 0.
+            const bool live = live_step == s;
+            const long long tend = live ? (long long)(s + 1) * f_cyc : TT;
             long long t1 = t + 1;
-            while (fuse && t1 < TT && !solves((int)(t1 % f_cyc))) ++t1;
+            while (fuse && t1 < tend && !solves((int)(t1 % f_cyc))) ++t1;
             for (int g = 0; g < G; ++g) {
                 Qn.C = grp[g].C;
                 Qn.t0 = t;
                 Qn.nt = (int)(t1 - t);
+                Qn.skip_anchored = live ? 1 : 0;
                 Qn.plan_traj = grp[g].plan_traj;
                 hipLaunchKernelGGL(cl_nominal_run_kernel, dim3(grp[g].g1), dim3(256), 0, grp[g].s, Qn);
                 HIPCHK(h, hipGetLastError());
+                if (live) {
+                    Qb.Q = Qn;
+                    Qb.xa = grp[g].xa; Qb.ua = grp[g].ua; Qb.du = grp[g].du;
+                    hipLaunchKernelGGL(cl_between_run_kernel, dim3(grp[g].g1), dim3(256), 0, grp[g].s, Qb);
+                    HIPCHK(h, hipGetLastError());
+                }
             }
             t = t1;
             continue;
@@ -1446,6 +1501,7 @@ static int closed_loop_impl(Handle* h, int64_t B, int32_t S, int32_t f_cyc, doub
         {   // a solve tick, as alipmpc_closed_loop_batch always ran it
             // rest_t = step_t - i * (step_t / f_cyc)   (main_sim_mpc.py:78)
             const double rest = T - i * (T / f_cyc);
+            const bool anchor = fo_mode && anchors(i);
             for (int g = 0; g < G; ++g) {
                 CLP& Cg = grp[g].C;
                 KP& Pg = grp[g].P;
@@ -1476,14 +1532,34 @@ static int closed_loop_impl(Handle* h, int64_t B, int32_t S, int32_t f_cyc, doub
                     HIPCHK(h, hipStreamSynchronize(sg));   // &base is a stack value
                 }
 #endif
-                HIPCHK(h, launch_solve(h, Pg, sg, h->cl_split_it, h->cl_split_tr));
+                // first-order mode, a later tick of the step does not solve: the sensitivity build's launch (the solve's
+                // own bits, DESIGN.md §3.7) on the group's queue pair, du straight into the group's anchors
+                if (anchor) {
+                    KP Ps = Pg;
+                    Ps.order = nullptr;
+                    Ps.grad_out = grp[g].dfoot;
+                    Ps.J_out = grp[g].du;
+                    Ps.active_out = reinterpret_cast<int8_t*>(grp[g].ok);
+                    HIPCHK(h, launch_sens(h, Ps, sg));
+                } else {
+                    HIPCHK(h, launch_solve(h, Pg, sg, h->cl_split_it, h->cl_split_tr));
+                }
                 hipLaunchKernelGGL(cl_update_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Cg);
                 HIPCHK(h, hipGetLastError());
                 if (grp[g].plan_traj) {
                     hipLaunchKernelGGL(cl_plan_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Cg, grp[g].plan_traj);
                     HIPCHK(h, hipGetLastError());
                 }
+                if (anchor || live_step == s) {   // (a live anchor bit is cleared by the step's first tick without one)
+                    CLA A;
+                    std::memset(&A, 0, sizeof(A));
+                    A.B = Cg.B; A.n = n; A.have = anchor ? 1 : 0; A.active = Cg.active; A.flags = Cg.flags;
+                    A.xs = Cg.xs; A.u = Cg.u; A.ok = grp[g].ok; A.xa = grp[g].xa; A.ua = grp[g].ua;
+                    hipLaunchKernelGGL(cl_anchor_kernel, dim3(grp[g].g1), dim3(256), 0, sg, A);
+                    HIPCHK(h, hipGetLastError());
+                }
             }
+            live_step = anchor ? s : -1;
         }
     }
     if (G > 1) {   // join
