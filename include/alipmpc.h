@@ -159,14 +159,20 @@ typedef struct alipmpc_cfg {
     int32_t cl_between;    /* what a tick of alipmpc_closed_loop_schedule_batch that does not solve commands (no other
                            entry point reads it): ALIPMPC_CL_BETWEEN_NOMINAL (0, default) — the nominal ALIP foothold;
                            ALIPMPC_CL_BETWEEN_FIRST_ORDER (1) — the last solve's plan moved to first order with the
-                           plant, where that solve's sensitivities are valid (see that entry point).  Mode 1 needs the
+                           plant, where that solve's sensitivities are valid (see that entry point);
+                           ALIPMPC_CL_BETWEEN_GUARDED (3) — mode 1 with every moved plan held against the constraint
+                           rows first: an episode whose plan fails re-solves on that tick.  Modes 1 and 3 need the
                            domain of alipmpc_solve_sens_batch: fp32, the lane program, DD or N = 6 make alipmpc_create
-                           return ALIPMPC_EUNSUPPORTED; any other value ALIPMPC_EINVAL.  (The former reserved_ field:
-                           sizeof(alipmpc_cfg) is unchanged.) */
+                           return ALIPMPC_EUNSUPPORTED; any other value (2 included) ALIPMPC_EINVAL.  (The former
+                           reserved_ field: sizeof(alipmpc_cfg) is unchanged.) */
 } alipmpc_cfg;
 
 #define ALIPMPC_CL_BETWEEN_NOMINAL 0
 #define ALIPMPC_CL_BETWEEN_FIRST_ORDER 1
+#define ALIPMPC_CL_BETWEEN_GUARDED 3
+/* the guard's bar on a first-order plan's largest constraint violation (mode 3): alipmpc_audit_batch's customary
+ * viol_tol and the restoration's local-infeasibility test */
+#define ALIPMPC_CL_GUARD_VIOL 1e-4
 
 #define ALIPMPC_GOAL_SINGULAR_ZERO 0
 #define ALIPMPC_GOAL_SINGULAR_ABORT 1
@@ -400,6 +406,31 @@ int alipmpc_closed_loop_dataset_batch(void* handle, int64_t B, int32_t S, int32_
  * group — the nominal kernel for the episodes without a valid anchor (so that their ticks have mode 0's bits) and a
  * first-order kernel for the others; before a step's first such solve, the nominal launch alone, as in mode 0.  The
  * anchors (B x (5 + 5N + 35N + 21) doubles) live in the handle's workspace in both pointer modes.
+ *
+ * Guarded first-order ticks (cfg.cl_between = ALIPMPC_CL_BETWEEN_GUARDED): mode 1, except that a first-order tick is
+ * accepted only if its plan passes the constraint rows, and an episode whose plan fails re-solves on that tick.
+ *   On a non-solve tick of an episode with a valid anchor, x_nex and u_fo are formed as above and viol = the largest
+ *   max(cl - c, c - cu, 0) over the rows alipmpc_eval_batch returns for (x0 = x_nex, u = u_fo, leg = -leg_ind),
+ *   obstacles selected at this x_nex: column 0 of alipmpc_audit_batch for those inputs.  The guard fires iff
+ *   !(viol <= ALIPMPC_CL_GUARD_VIOL) — a NaN (a plan or state that is not finite) fires.
+ *   Not fired: mode 1's first-order tick, bit for bit.
+ *   Fired: a solve tick for that episode alone — the projection of a solve tick, warm start = the loop's current plan
+ *   (the previous tick's u_fo, or the anchor plan), alipmpc_solve_sens_batch's launch restricted to the fired episodes,
+ *   the solve tick's update.  status_traj and iters_traj hold the solve's values and the plan_traj row its u, so a
+ *   triggered tick is one whose mask bit is clear and whose status is none of ALIPMPC_ROLLOUT_DONE, ALIPMPC_TICK_NOMINAL
+ *   and ALIPMPC_TICK_FIRST_ORDER.  The solve replaces the anchor when sens_ok and a later tick of the step does not
+ *   solve by the mask; otherwise the episode has no anchor until the step's next solve and its ticks are nominal.
+ *   Episodes without an anchor run the nominal tick with mode 0's bits; a touchdown invalidates the anchor as before.
+ * Not guarded: nominal ticks, and the dense trace's clearance (alipmpc_audit_batch's other columns).  There is no cap
+ * on the re-solves of a step.  Only this entry point reads the mode: elsewhere a mode-3 handle is a mode-0 handle, and
+ * here with the all-ones mask or mask 0 as well.
+ * Launches: after a solve left anchors, the non-solve ticks of the step run one at a time, each as the nominal launch
+ * (episodes without an anchor), the guard (cl_guard_kernel: the audit's violation pass on 16-lane groups, which marks
+ * the fired episodes), the first-order launch (skips them) and the solve tick's launches acting on the fired episodes
+ * alone — every one issued whether or not an episode fired: the host never learns the count, and device-pointer calls
+ * stay copy-free and synchronisation-free.  Before a step's first anchor the launches are mode 0's.
+ * ALIPMPC_CL_GUARD_TOL (development, read per call as ALIPMPC_CL_FUSE is) replaces the bar: a number as strtod reads
+ * it; inf never fires on a finite plan, a negative value always fires; empty, unparsable or NaN: the default.
  */
 #define ALIPMPC_TICK_NOMINAL (-20)       /* status_traj: the tick ran the nominal ALIP law, no solve */
 #define ALIPMPC_TICK_FIRST_ORDER (-21)   /* status_traj: the tick moved the last solve's plan to first order, no solve */

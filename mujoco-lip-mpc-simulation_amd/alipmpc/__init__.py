@@ -10,7 +10,7 @@
 from ._lib import (Cfg, Solver, default_cfg, load, lib_path, build_id, num_vars, rows_per_step, trace_len, audit_summary_len,
                    EXPORTS, STATUS_NAMES,
                    VARIANT_MODI, VARIANT_SIG_STEP, VARIANT_DD, PREC_FP64, PREC_FP32, PROGRAM_WAVE, PROGRAM_LANE,
-                   ROLLOUT_DONE, TICK_NOMINAL, TICK_FIRST_ORDER, CL_BETWEEN_NOMINAL, CL_BETWEEN_FIRST_ORDER, FP32_TOL,
+                   ROLLOUT_DONE, TICK_NOMINAL, TICK_FIRST_ORDER, CL_BETWEEN_NOMINAL, CL_BETWEEN_FIRST_ORDER, CL_BETWEEN_GUARDED, CL_GUARD_VIOL, FP32_TOL,
                    FP32_ACCEPTABLE_TOL, FP32_TOL_LONG, FP32_ACCEPTABLE_TOL_LONG, GOAL_SINGULAR_ZERO,
                    GOAL_SINGULAR_ABORT, INVALID_NUMBER_DETECTED, RESTORATION_IPOPT, RESTORATION_SUBSTITUTE)
 
@@ -18,6 +18,6 @@ __all__ = ["Cfg", "Solver", "default_cfg", "load", "lib_path", "build_id", "num_
            "EXPORTS",
            "STATUS_NAMES", "VARIANT_MODI", "VARIANT_SIG_STEP", "VARIANT_DD", "PREC_FP64", "PREC_FP32",
            "PROGRAM_WAVE", "PROGRAM_LANE", "ROLLOUT_DONE", "TICK_NOMINAL", "TICK_FIRST_ORDER",
-           "CL_BETWEEN_NOMINAL", "CL_BETWEEN_FIRST_ORDER", "FP32_TOL", "FP32_ACCEPTABLE_TOL",
+           "CL_BETWEEN_NOMINAL", "CL_BETWEEN_FIRST_ORDER", "CL_BETWEEN_GUARDED", "CL_GUARD_VIOL", "FP32_TOL", "FP32_ACCEPTABLE_TOL",
            "FP32_TOL_LONG", "FP32_ACCEPTABLE_TOL_LONG", "GOAL_SINGULAR_ZERO", "GOAL_SINGULAR_ABORT",
            "INVALID_NUMBER_DETECTED", "RESTORATION_IPOPT", "RESTORATION_SUBSTITUTE"]

@@ -29,6 +29,8 @@ ROLLOUT_DONE = -10
 TICK_NOMINAL = -20   # closed_loop_schedule: the tick ran the nominal ALIP law, no solve (ALIPMPC_TICK_NOMINAL)
 TICK_FIRST_ORDER = -21   # ... the tick moved the last solve's plan to first order (ALIPMPC_TICK_FIRST_ORDER)
 CL_BETWEEN_NOMINAL, CL_BETWEEN_FIRST_ORDER = 0, 1   # cfg.cl_between (include/alipmpc.h)
+CL_BETWEEN_GUARDED = 3    # ... first-order ticks held against the constraint rows, re-solve on violation
+CL_GUARD_VIOL = 1e-4      # ... its bar on the largest violation (ALIPMPC_CL_GUARD_VIOL)
 
 _ERRORS = {-1: "EINVAL", -2: "ENODEV (no visible gfx950 device)", -3: "EHIP", -4: "EUNSUPPORTED"}
 
@@ -487,7 +489,11 @@ class Solver:
         On a handle whose cfg.cl_between is CL_BETWEEN_FIRST_ORDER, a tick between the solves of a step whose last
         solve has valid sensitivities commands that solve's plan moved to first order with the plant instead, u_fo =
         u + du[:, 0:5] (x_nex - x_nex of the solve): status TICK_FIRST_ORDER (-21), 0 iterations, plan row u_fo; the
-        ticks before a step's first solve, and those after a solve without valid sensitivities, stay nominal."""
+        ticks before a step's first solve, and those after a solve without valid sensitivities, stay nominal.
+        cfg.cl_between = CL_BETWEEN_GUARDED (3): the same, but u_fo is first held against the constraint rows at the
+        tick's x_nex (audit's viol of (x_nex, u_fo, -leg_ind)); where it exceeds CL_GUARD_VIOL the episode re-solves on
+        that tick, warm-started from its current plan, and takes a new anchor: the tick then carries the solve's status,
+        iterations and plan although it is not in mpc_ticks."""
         from .schedule import mask_of
         sc = dict(S=int(steps), f_cyc=int(f_cyc), mpc_mask=mask_of(mpc_ticks), kick=float(kick), seed=int(seed))
         return self._host("alipmpc_closed_loop_schedule_batch",
@@ -497,7 +503,8 @@ class Solver:
     def closed_loop_schedule_device(self, inp, out, steps, f_cyc=20, mpc_ticks=(15,), kick=0.0, seed=0, stream=None):
         """Asynchronous scheduled closed loop on device tensors: inp / out as closed_loop_device, out also with plan
         (B, S, f_cyc, 5N) if the plans are wanted.  cfg.cl_between = CL_BETWEEN_FIRST_ORDER: first-order ticks (status
-        TICK_FIRST_ORDER, -21) as in closed_loop_schedule."""
+        TICK_FIRST_ORDER, -21) as in closed_loop_schedule; CL_BETWEEN_GUARDED (3): guarded ones, with re-solves on the
+        device where the guard fires (no host round trip)."""
         from .schedule import mask_of
         self._device("alipmpc_closed_loop_schedule_batch", inp, out, stream, inp["x0"].shape[0], int(steps), int(f_cyc),
                      mask_of(mpc_ticks), float(kick), int(seed))

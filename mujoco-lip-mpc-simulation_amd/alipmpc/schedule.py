@@ -4,13 +4,14 @@ main_sim_mpc_alip.py:71-130 on an ALIP plant.  Tick i of a step solves the MPC w
 the plant's projection (Logger.cal_foot_input, data_procs/logger.py:380-410: cal_foot_with_veldes(x_nex, v_des_map)).
 
   run     drives the loop with any solver (a callable): the host restatement of the device loop, in either mode of
-          cfg.cl_between (nominal or first-order ticks between the solves)
+          cfg.cl_between (nominal, first-order or guarded first-order ticks between the solves)
   replay  recomputes every step of a device loop from the device's own touchdown state x[:, s] and its recorded plans,
           so no drift crosses a step; also returns the solve inputs (x_nex, -leg_ind, u0) of every solved tick
 
 Built from the pieces of alipmpc.tsc (heading tube, command packing) and alipmpc.planner (ALIP matrices); every
 expression is written in the operation order of the device kernels (csrc/alipmpc.hip: cl_project_kernel,
-cl_update_kernel, cl_nominal_run_kernel, cl_between_run_kernel / cl_first_order_plan, nominal_gait_kernel).
+cl_update_kernel, cl_nominal_run_kernel, cl_between_run_kernel / cl_first_order_plan, nominal_gait_kernel; the guard of
+the guarded mode is csrc/audit.inc's cl_guard_kernel).
 """
 import math
 from fractions import Fraction
@@ -22,6 +23,8 @@ from . import planner, tsc
 TICK_NOMINAL = -20     # ALIPMPC_TICK_NOMINAL
 TICK_FIRST_ORDER = -21  # ALIPMPC_TICK_FIRST_ORDER
 BETWEEN_NOMINAL, BETWEEN_FIRST_ORDER = 0, 1   # cfg.cl_between
+BETWEEN_GUARDED = 3     # ... first-order ticks behind the guard (ALIPMPC_CL_BETWEEN_GUARDED)
+GUARD_VIOL = 1e-4       # ALIPMPC_CL_GUARD_VIOL: the guard's bar on a first-order plan's largest violation
 ROLLOUT_DONE = -10     # ALIPMPC_ROLLOUT_DONE
 VARIANT_MODI, VARIANT_SIG_STEP = 0, 1
 MAX_F_CYC = 64
@@ -113,9 +116,10 @@ def _fma(a, b, c):
 
 def flow_device(x, fx, fy, hp, ch, shb, bsh, tt, project):
     """flow() with the roundings of the device kernels, which contract cl_flow's expressions into fma's: position
-    fma(1 - ch, f, fma(ch, pos, shb vel)) and heading fma(tt, hp, x4) in both; velocity fma(-bsh, f, fma(bsh, pos,
-    ch vel)) in cl_project_kernel (project: a solve tick's x_nex) and fma(-f, bsh, fma(ch, vel, bsh pos)) in
-    cl_nominal_run_kernel's plant move.  (Read off the gfx950 code of the two kernels; replay's bit-exact mode.)"""
+    fma(1 - ch, f, fma(ch, pos, shb vel)) and heading fma(tt, hp, x4) in all; velocity fma(-bsh, f, fma(bsh, pos,
+    ch vel)) in cl_project_kernel (project: a solve tick's x_nex) and in the plant moves of cl_update_kernel and
+    cl_between_run_kernel (a tick with a plan), and fma(-f, bsh, fma(ch, vel, bsh pos)) in cl_nominal_run_kernel's
+    plant move.  (Read off the gfx950 code of the kernels; replay's bit-exact mode.)"""
     omc = 1.0 - ch
     cols = []
     for pos, vel, f in ((x[:, 0], x[:, 2], fx), (x[:, 1], x[:, 3], fy)):
@@ -215,7 +219,7 @@ def _close(variant, xp, goal):
     return (d <= 0.35).any(1) if variant == VARIANT_SIG_STEP else d[:, 0] <= 0.15
 
 
-def _loop(cfg, inp, mask, steps, f_cyc, kick, seed, solve, dev, between=BETWEEN_NOMINAL, sens=None):
+def _loop(cfg, inp, mask, steps, f_cyc, kick, seed, solve, dev, between=BETWEEN_NOMINAL, sens=None, guard=None):
     k = constants(cfg)
     N, n, variant = k["N"], 5 * k["N"], k["variant"]
     S, F = int(steps), int(f_cyc)
@@ -250,12 +254,62 @@ def _loop(cfg, inp, mask, steps, f_cyc, kick, seed, solve, dev, between=BETWEEN_
     solves = dict(b=[], s=[], i=[], x_nex=[], leg=[], u0=[])
     # first-order mode: the anchor of every episode (the last solve of the current step: its x_nex, plan, du[:, :, 0:5]
     # and tick), valid where that solve's sens_ok is set and no touchdown came since
-    fo_mode = int(between) == BETWEEN_FIRST_ORDER
+    guarded = int(between) == BETWEEN_GUARDED
+    fo_mode = int(between) == BETWEEN_FIRST_ORDER or guarded
     exact = dev is not None and dev.get("hd") is not None and dev.get("foot") is not None
     a_x, a_u, a_du = np.zeros((B, 5)), np.zeros((B, n)), np.zeros((B, n, 5))
     a_ok, a_i = np.zeros(B, bool), np.full(B, -1)
     fos = dict(b=[], s=[], i=[], x_nex=[], anchor_i=[])
     anchors = dict(b=[], s=[], i=[], sens_ok=[], du=[])
+    trigs = dict(b=[], s=[], i=[], x_nex=[], u0=[])
+
+    def solve_tick(s, i, sel, xn, triggered):
+        """The solve tick of the episodes sel (x_nex xn): the whole tick's, or a guarded tick's re-solve.  Returns the
+        foothold, the predicted states and close_2_goal."""
+        m = len(sel)
+        u0 = np.tile(xn, (1, N))
+        hp_ = has_plan[sel]
+        if variant == VARIANT_SIG_STEP:
+            pb = plan[sel].reshape(m, N, 5)
+            u0[hp_] = np.concatenate([pb[:, 1:], pb[:, -1:]], axis=1).reshape(m, n)[hp_]
+        else:
+            u0[hp_] = plan[sel][hp_]
+        od = (-leg[sel]).astype(np.int8)
+        if dev is not None:
+            u = np.asarray(dev["plan"])[sel, s, i]
+            ft, xp = plan_outputs(k, xn, u)
+            o = dict(u=u, foot=ft, x_pred=xp, status=np.asarray(dev["status"])[sel, s, i], iters=np.zeros(m, np.int32))
+            if triggered:
+                for key, v in (("b", sel), ("s", np.full(m, s)), ("i", np.full(m, i)), ("x_nex", xn), ("u0", u0)):
+                    trigs[key].append(v)
+            else:
+                for key, v in (("b", sel), ("s", np.full(m, s)), ("i", np.full(m, i)), ("x_nex", xn), ("leg", od),
+                               ("u0", u0)):
+                    solves[key].append(v)
+        else:
+            o = solve(xn, od, u0, sel)
+        if fo_mode:   # a later tick of the step does not solve: this solve leaves the anchor
+            if (all_ones(F) & ~mask) >> (i + 1):
+                du_, ok_ = sens(xn, od, u0, sel) if dev is not None else (o["du"], o["sens_ok"])
+                ok_ = np.asarray(ok_).reshape(m) != 0
+                du_ = np.asarray(du_, np.float64).reshape(m, n, -1)
+                a_ok[sel] = ok_
+                j = sel[ok_]
+                a_x[j], a_u[j], a_du[j], a_i[j] = xn[ok_], np.asarray(o["u"])[ok_], du_[ok_][:, :, 0:5], i
+                for key, v in (("b", sel), ("s", np.full(m, s)), ("i", np.full(m, i)), ("sens_ok", ok_), ("du", du_)):
+                    anchors[key].append(v)
+            else:
+                a_ok[sel] = False
+        status[sel, s, i] = o["status"]
+        iters[sel, s, i] = o["iters"]
+        plan[sel] = o["u"]
+        plans[sel, s, i] = o["u"]
+        has_plan[sel] = True
+        nex_turn[sel] = o["foot"][:, 2]
+        xp = np.asarray(o["x_pred"]).reshape(m, N, 5)
+        mhd[sel, :min(3, N)] = xp[:, :3, 4]
+        return np.asarray(o["foot"])[:, 0:2], xp, _close(variant, xp, goal[sel])
+
     for s in range(S):
         if dev is not None:   # replay: every step from the device's own touchdown state and its set of episodes
             x = np.array(dev["x"][:, s], np.float64)
@@ -285,83 +339,69 @@ def _loop(cfg, inp, mask, steps, f_cyc, kick, seed, solve, dev, between=BETWEEN_
             solved = bool(mask >> i & 1)
             xn = (flow_device(xi, fx, fy, hp, ch_r, shb_r, bsh_r, tr, True) if exact and solved else
                   flow(xi, fx, fy, hp, ch_r, shb_r, bsh_r, tr))
+            # upd: the episodes whose tick has a plan (solved, first-order or re-solved), xp / close: what follows from it
+            upd = np.zeros(len(idx), bool)
+            xp = np.full((len(idx), N, 5), np.nan)
+            close = np.zeros(len(idx), bool)
+            fo = np.zeros(len(idx), bool)
             if solved:
-                u0 = np.tile(xn, (1, N))
-                hp_ = has_plan[idx]
-                if variant == VARIANT_SIG_STEP:
-                    pb = plan[idx].reshape(len(idx), N, 5)
-                    u0[hp_] = np.concatenate([pb[:, 1:], pb[:, -1:]], axis=1).reshape(len(idx), n)[hp_]
-                else:
-                    u0[hp_] = plan[idx][hp_]
-                od = (-leg[idx]).astype(np.int8)
-                if dev is not None:
-                    u = np.asarray(dev["plan"])[idx, s, i]
-                    ft, xp = plan_outputs(k, xn, u)
-                    o = dict(u=u, foot=ft, x_pred=xp, status=np.asarray(dev["status"])[idx, s, i],
-                             iters=np.zeros(len(idx), np.int32))
-                    for key, v in (("b", idx), ("s", np.full(len(idx), s)), ("i", np.full(len(idx), i)),
-                                   ("x_nex", xn), ("leg", od), ("u0", u0)):
-                        solves[key].append(v)
-                else:
-                    o = solve(xn, od, u0, idx)
-                if fo_mode:   # a later tick of the step does not solve: this solve leaves the anchor
-                    if (all_ones(F) & ~mask) >> (i + 1):
-                        du_, ok_ = sens(xn, od, u0, idx) if dev is not None else (o["du"], o["sens_ok"])
-                        ok_ = np.asarray(ok_).reshape(len(idx)) != 0
-                        du_ = np.asarray(du_, np.float64).reshape(len(idx), n, -1)
-                        a_ok[idx] = ok_
-                        j = idx[ok_]
-                        a_x[j], a_u[j], a_du[j], a_i[j] = xn[ok_], np.asarray(o["u"])[ok_], du_[ok_][:, :, 0:5], i
-                        for key, v in (("b", idx), ("s", np.full(len(idx), s)), ("i", np.full(len(idx), i)),
-                                       ("sens_ok", ok_), ("du", du_)):
-                            anchors[key].append(v)
-                    else:
-                        a_ok[idx] = False
-                status[idx, s, i] = o["status"]
-                iters[idx, s, i] = o["iters"]
-                plan[idx] = o["u"]
-                plans[idx, s, i] = o["u"]
-                has_plan[idx] = True
-                nex_turn[idx] = o["foot"][:, 2]
-                xp = np.asarray(o["x_pred"]).reshape(len(idx), N, 5)
-                mhd[idx, :min(3, N)] = xp[:, :3, 4]
-                close = _close(variant, xp, goal[idx])
-                nfoot = np.asarray(o["foot"])[:, 0:2]
-                fo = np.zeros(len(idx), bool)
+                nfoot, xp, close = solve_tick(s, i, idx, xn, False)
+                upd[:] = True
             else:
                 nfoot = foot_with_veldes(k, xn, vdes[idx])
                 status[idx, s, i] = TICK_NOMINAL
                 iters[idx, s, i] = 0
                 # first-order ticks: the episodes with a valid anchor (replay: the ticks the device ran as such)
-                fo = np.zeros(len(idx), bool)
+                trig = np.zeros(len(idx), bool)
                 if fo_mode:
-                    fo = np.asarray(dev["status"])[idx, s, i] == TICK_FIRST_ORDER if dev is not None else a_ok[idx]
-                if fo.any():   # a solve tick whose outputs follow from u_fo
+                    st_dev = np.asarray(dev["status"])[idx, s, i] if dev is not None else None
+                    fo = st_dev == TICK_FIRST_ORDER if dev is not None else a_ok[idx].copy()
+                    if guarded and dev is not None:   # the device recorded a solve on a tick outside the mask
+                        trig = ~np.isin(st_dev, (ROLLOUT_DONE, TICK_NOMINAL, TICK_FIRST_ORDER))
+                u_fo = None
+                if fo.any():
                     j = idx[fo]
-                    u_fo, ft, xp = first_order_plan(k, xn[fo], a_x[j], a_u[j], a_du[j])
+                    u_fo, ft, xpf = first_order_plan(k, xn[fo], a_x[j], a_u[j], a_du[j])
+                    if guarded and dev is None:   # the guard: the rows at this x_nex, obstacles selected there
+                        v = np.asarray(guard["viol"](xn[fo], (-leg[j]).astype(np.int8), u_fo, j), float).reshape(len(j))
+                        fired = ~(v <= guard["tol"])
+                        trig[np.nonzero(fo)[0][fired]] = True
+                        keep = ~fired
+                        fo[trig] = False
+                        j, u_fo, ft, xpf = j[keep], u_fo[keep], ft[keep], xpf[keep]
+                if fo.any():   # a solve tick whose outputs follow from u_fo
                     status[j, s, i] = TICK_FIRST_ORDER
                     # (bit-exact replay: the next solve's warm start is the device's row, the replay's own is returned)
                     plan[j] = np.asarray(dev["plan"])[j, s, i] if exact else u_fo
                     plans[j, s, i] = u_fo
                     nex_turn[j] = ft[:, 2]
-                    mhd[j, :min(3, N)] = xp[:, :3, 4]
-                    close = _close(variant, xp, goal[j])
+                    mhd[j, :min(3, N)] = xpf[:, :3, 4]
+                    xp[fo], close[fo], upd[fo] = xpf, _close(variant, xpf, goal[j]), True
                     nfoot[fo] = ft[:, 0:2]
                     for key, v in (("b", j), ("s", np.full(len(j), s)), ("i", np.full(len(j), i)), ("x_nex", xn[fo]),
                                    ("anchor_i", a_i[j])):
                         fos[key].append(v)
+                if trig.any():   # guarded mode: the fired episodes' solve tick (the projection of a solve tick)
+                    if exact:
+                        xn[trig] = flow_device(xi[trig], fx[trig], fy[trig], hp[trig], ch_r, shb_r, bsh_r, tr, True)
+                    nfoot[trig], xp[trig], close[trig] = solve_tick(s, i, idx[trig], xn[trig], True)
+                    upd[trig] = True
             target[idx, s, i] = nfoot
             action[idx, s, i] = command(pose0[idx], nfoot, fx, fy, xn, vdes[idx], xi[:, 4], hp, hd_cos[idx], i, F)
-            if solved or fo.any():   # vel_des <- mpc_state_tar[0][2:4] after a solve, [1][2:4] at touchdown
+            if upd.any():   # vel_des <- mpc_state_tar[0][2:4] after a solve, [1][2:4] at touchdown
                 kv = 1 if (i == F - 1 and N > 1) else 0
-                vdes[idx[fo] if not solved else idx] = xp[:, kv, 2:4]
-            nominal_move = exact and not solved and not fo.any()   # (the move of cl_nominal_run_kernel, to the bit)
-            xa = (flow_device(xi, fx, fy, hp, ch_d, shb_d, bsh_d, td, False) if nominal_move else
-                  flow(xi, fx, fy, hp, ch_d, shb_d, bsh_d, td))
+                vdes[idx[upd]] = xp[upd][:, kv, 2:4]
+            if exact:   # the plant move to the bit: cl_nominal_run_kernel's form, or the tick kernels' after a plan
+                xa = np.empty_like(xi)
+                for sel, form in ((upd, True), (~upd, False)):
+                    if sel.any():
+                        xa[sel] = flow_device(xi[sel], fx[sel], fy[sel], hp[sel], ch_d, shb_d, bsh_d, td, form)
+            else:
+                xa = flow(xi, fx, fy, hp, ch_d, shb_d, bsh_d, td)
             if kick > 0:
                 for ax in (0, 1):
                     kv_ = np.array([2.0 * cl_uniform(seed, int(b), s, i, ax) - 1.0 for b in idx])
-                    xa[:, 2 + ax] = _fma(kick, kv_, xa[:, 2 + ax]) if nominal_move else xa[:, 2 + ax] + kick * kv_
+                    xa[:, 2 + ax] = _fma(kick, kv_, xa[:, 2 + ax]) if exact else xa[:, 2 + ax] + kick * kv_
             x[idx] = xa
             if i == F - 1:   # touchdown
                 pst[idx] = nfoot
@@ -371,15 +411,12 @@ def _loop(cfg, inp, mask, steps, f_cyc, kick, seed, solve, dev, between=BETWEEN_
                 if not solved:
                     pl = plan[idx].reshape(len(idx), N, 5)[:, 1 if N > 1 else 0, 2:4]
                     nominal = np.where(has_plan[idx, None], pl, des_vel(k, leg[idx]))
-                    vdes[idx] = np.where(fo[:, None], vdes[idx], nominal)   # (a first-order tick took its own)
+                    vdes[idx] = np.where(upd[:, None], vdes[idx], nominal)   # (a tick with a plan took its own)
                 stop = idx[rclose[idx]]
                 active[stop] = False
                 stg[stop] = s + 1
                 a_ok[idx] = False   # the linearisation does not carry over a touchdown
-            if solved:
-                rclose[idx] |= close
-            elif fo.any():
-                rclose[idx[fo]] |= close
+            rclose[idx[upd]] |= close[upd]
         xs[:, s + 1] = x
     out = dict(foot=foot, x=xs, hd=hd, status=status, iters=iters, steps_to_goal=stg, action=action, plan=plans,
                target=target)
@@ -395,32 +432,46 @@ def _loop(cfg, inp, mask, steps, f_cyc, kick, seed, solve, dev, between=BETWEEN_
             out["anchors"] = dict(b=ci(anchors["b"]), s=ci(anchors["s"]), i=ci(anchors["i"]),
                                   sens_ok=cat(anchors["sens_ok"], (0,)).astype(bool),
                                   du=cat(anchors["du"], (0, n, 7)))
+        if guarded:
+            out["triggered"] = dict(b=ci(trigs["b"]), s=ci(trigs["s"]), i=ci(trigs["i"]),
+                                    x_nex=cat(trigs["x_nex"], (0, 5)), u0=cat(trigs["u0"], (0, n)))
     return out
 
 
 def _between(cfg, between):
     b = int(getattr(cfg, "cl_between", BETWEEN_NOMINAL) if between is None else between)
-    if b not in (BETWEEN_NOMINAL, BETWEEN_FIRST_ORDER):
+    if b not in (BETWEEN_NOMINAL, BETWEEN_FIRST_ORDER, BETWEEN_GUARDED):
         raise ValueError(f"between = {b}")
     return b
 
 
-def run(cfg, inputs, mask, solve=None, steps=8, f_cyc=20, kick=0.0, seed=0, between=None):
+def run(cfg, inputs, mask, solve=None, steps=8, f_cyc=20, kick=0.0, seed=0, between=None, guard_tol=GUARD_VIOL,
+        viol=None):
     """The scheduled loop on the host.  cfg: an object with N, variant, dt, g, H (a Cfg); inputs: dict with x0 (B, 5),
     foot0 (B, 2), goal, leg; mask: int mask or iterable of solved ticks; solve(x_nex (n, 5), od_ev (n,), u0 (n, 5N),
     idx (n,) the episodes) -> dict(u, foot, x_pred, status, iters) — not needed for mask 0.  between: what a tick
     without a solve does, BETWEEN_NOMINAL or BETWEEN_FIRST_ORDER (None: cfg.cl_between, 0 where cfg has none); in
     first-order mode solve's dict also carries du (n, 5N, 7) and sens_ok (n,) (Solver.solve_sens's), and a tick with a
     valid anchor moves the anchor's plan by du[:, :, 0:5] (x_nex - x_nex of the anchor) (status TICK_FIRST_ORDER).
+    BETWEEN_GUARDED: the first-order mode with the guard — viol(x_nex (m, 5), od_ev (m,), u (m, 5N), idx (m,)) -> (m,)
+    is the largest constraint violation of the moved plan at the tick's x_nex (Solver.audit's column 0; audit.
+    audit_reference's on the host); where not viol <= guard_tol (a NaN fires) the episode solves on that tick instead,
+    warm-started from its current plan, and the solve leaves the new anchor (or none, as a scheduled solve would).
     Returns the dict of Solver.closed_loop_schedule (plan included, NaN rows on nominal ticks and after the stop) plus
     target (B, S, f_cyc, 2): the foothold every tick commands."""
     if solve is None and mask_of(mask, f_cyc):
         raise ValueError("a schedule with solved ticks needs a solve callable")
-    return _loop(cfg, inputs, mask, steps, f_cyc, float(kick), int(seed), solve, None, _between(cfg, between))
+    between = _between(cfg, between)
+    guard = None
+    if between == BETWEEN_GUARDED:
+        if viol is None:
+            raise ValueError("between = BETWEEN_GUARDED needs a viol callable")
+        guard = dict(tol=float(guard_tol), viol=viol)
+    return _loop(cfg, inputs, mask, steps, f_cyc, float(kick), int(seed), solve, None, between, guard=guard)
 
 
 def replay(cfg, inputs, mask, x_traj, plan_traj, status_traj, kick=0.0, seed=0, sens=None, foot_traj=None,
-           hd_traj=None):
+           hd_traj=None, guarded=False):
     """Every step of a device loop recomputed from the device's own touchdown state x_traj[:, s], the episodes it
     still ran (status_traj[:, s, 0]) and the plans it recorded (plan_traj), a solve's foothold and predicted states
     derived from its plan as gen_control_test does (plan_outputs).  Returns foot, hd, x (x[:, s + 1] from
@@ -435,12 +486,20 @@ def replay(cfg, inputs, mask, x_traj, plan_traj, status_traj, kick=0.0, seed=0, 
     stance foot and heading inputs as well, the plant moves of the nominal ticks and the projection of a solve tick
     round as the device kernels do (flow_device), and the warm start after a first-order tick is the device's recorded
     row — so that up to a step's first solve x_nex and u0 are the device's own bits, and a solve of them on the same
-    handle is the device's solve.  (A step in which a nominal tick follows a solve or first-order tick is exact up to
-    that solve only; the other outputs are compared within a tolerance either way.)"""
+    handle is the device's solve.  The plant moves after a solve or first-order tick round as cl_update_kernel's and
+    cl_between_run_kernel's do, so a later solve of the step — a guarded loop's re-solve — has the device's inputs too.
+    (The other outputs are compared within a tolerance either way.)
+    guarded (with sens; a handle with cfg.cl_between = 3): a tick outside the mask on which the device recorded a solve
+    status is replayed as that episode's solve tick — x_nex by the projection's roundings, warm start from the plan as
+    it stands, the recorded plan row as its u, the new anchor from sens — and the result also holds triggered: dict(b,
+    s, i, x_nex, u0), those ticks with their solve inputs.  anchors then lists the re-solves' anchors too (their i is
+    outside the mask)."""
     st = np.asarray(status_traj)
     B, S, F = st.shape
     dev = dict(x=np.asarray(x_traj, np.float64), plan=np.asarray(plan_traj, np.float64).reshape(B, S, F, -1), status=st,
                foot=None if foot_traj is None else np.asarray(foot_traj, np.float64),
                hd=None if hd_traj is None else np.asarray(hd_traj, np.float64))
+    if guarded and sens is None:
+        raise ValueError("a guarded replay needs sens")
     return _loop(cfg, inputs, mask, S, F, float(kick), int(seed), None, dev,
-                 BETWEEN_NOMINAL if sens is None else BETWEEN_FIRST_ORDER, sens)
+                 BETWEEN_NOMINAL if sens is None else BETWEEN_GUARDED if guarded else BETWEEN_FIRST_ORDER, sens)

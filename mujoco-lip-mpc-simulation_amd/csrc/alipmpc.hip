@@ -4848,13 +4848,17 @@ __device__ inline double veldes_foot(double bsh, double ch, double ibv, double p
     return ibv * (vd - a);
 }
 
-__global__ __launch_bounds__(256) void cl_project_kernel(CLP C)
+// fired_only (the guarded mode's re-solve of a tick, cl_guard_kernel): the episodes with CL_FLAG_FIRED alone are
+// projected and solved; cl_update_kernel and cl_plan_kernel then leave the others' state and rows as they are
+constexpr uint8_t CL_FLAG_FIRED = 16;   // CLP::flags bit 4: the guard fired on this tick (cleared by cl_anchor_kernel)
+__global__ __launch_bounds__(256) void cl_project_kernel(CLP C, int fired_only)
 {
     const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= C.B) return;
     const uint8_t fl = C.flags[b];
-    C.active[b] = fl & 1;
-    if (!(fl & 1)) return;
+    const bool on = (fl & 1) && (!fired_only || (fl & CL_FLAG_FIRED));
+    C.active[b] = on ? 1 : 0;
+    if (!on) return;
     double* x = C.x + 5 * b;
     double* hv = C.hdv + 4 * b;
     const double* mh = C.mhd + 3 * b;
@@ -4919,11 +4923,12 @@ __global__ __launch_bounds__(CL_ORDER_THREADS) void cl_order_kernel(const int32_
     for (long long b = t; b < B; b += CL_ORDER_THREADS) order[atomicAdd(&hist[key(b)], 1u)] = (int32_t)b;
 }
 
-__global__ __launch_bounds__(256) void cl_update_kernel(CLP C)
+__global__ __launch_bounds__(256) void cl_update_kernel(CLP C, int fired_only)
 {
     const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= C.B) return;
     uint8_t fl = C.flags[b];
+    if (fired_only && !(fl & CL_FLAG_FIRED)) return;
     const size_t ti = ((size_t)b * C.S + C.s) * C.f + C.i;
     if (!(fl & 1)) {
         if (C.status_traj) C.status_traj[ti] = ALIPMPC_ROLLOUT_DONE;
@@ -5285,7 +5290,7 @@ __global__ __launch_bounds__(256) void cl_anchor_kernel(CLA Q)
 {
     const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= Q.B || !Q.active[b]) return;
-    uint8_t fl = Q.flags[b] & (uint8_t)~CL_FLAG_ANCHOR;
+    uint8_t fl = Q.flags[b] & (uint8_t)~(CL_FLAG_ANCHOR | CL_FLAG_FIRED);   // (the guarded mode's re-solve ends here)
     if (Q.have && Q.ok[b] != 0) {
         for (int c = 0; c < 5; ++c) Q.xa[5 * b + c] = Q.xs[5 * b + c];
         for (int c = 0; c < Q.n; ++c) Q.ua[(size_t)b * Q.n + c] = Q.u[(size_t)b * Q.n + c];
@@ -5308,7 +5313,8 @@ __global__ __launch_bounds__(256) void cl_between_run_kernel(CLB F)
     const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= C.B) return;
     uint8_t fl = C.flags[b];
-    if (!(fl & 1) || !(fl & CL_FLAG_ANCHOR)) return;
+    // (guarded mode: an episode whose guard fired on this tick re-solves instead)
+    if (!(fl & 1) || !(fl & CL_FLAG_ANCHOR) || (fl & CL_FLAG_FIRED)) return;
     double x[5], hv[3], mh[3], p0[3];
     for (int c = 0; c < 5; ++c) x[c] = C.x[5 * b + c];
     for (int c = 0; c < 3; ++c) {
@@ -5372,13 +5378,15 @@ __global__ __launch_bounds__(256) void cl_between_run_kernel(CLB F)
 }
 
 // plan_traj row of a solved tick (after cl_update_kernel): the solve's u, NaN for an episode the tick did not solve
-__global__ __launch_bounds__(256) void cl_plan_kernel(CLP C, double* plan_traj)
+// (fired_only: the rows of the episodes it did not solve are the tick kernels')
+__global__ __launch_bounds__(256) void cl_plan_kernel(CLP C, double* plan_traj, int fired_only)
 {
     const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= C.B) return;
     const int n = 5 * C.N;
     const size_t ti = ((size_t)b * C.S + C.s) * C.f + C.i;
     const bool on = C.active[b] != 0;
+    if (fired_only && !on) return;
     for (int c = 0; c < n; ++c) plan_traj[ti * n + c] = on ? C.u[(size_t)b * n + c] : NAN;
 }
 

@@ -151,27 +151,14 @@ __device__ __forceinline__ void audit_rows(const KP& P, const AWS<N>& w, int t, 
     }
 }
 
-template <int N>
-__device__ __forceinline__ void audit_group_one(const AuP& A, const AWS<N>& w, const double* G, const double* E,
-                                                const double* tab, unsigned* cnt, long long b, int t)
+// The obstacles of instance b: the eval layout's select_obs compaction about (px, py) (eval_group_one's) into w.obs,
+// ncs circles and nes ellipses kept; AO: also, unfiltered, the audited list w.ao.
+template <int N, bool AO>
+__device__ __forceinline__ void audit_select(const KP& P, const AWS<N>& w, long long b, int t, double px, double py,
+                                             int ncr, int ner, int& ncs, int& nes)
 {
-    using D = Dim<N>;
-    constexpr int nu = D::nu, NCP = D::NCPU, NG = D::NG;
-    const KP& P = A.kp;
-    const gdouble* x0 = gptr(P.x0) + 5 * b;
-    const int legv = P.leg[b];
-    const int ncr = min(max(P.nc[b], 0), P.nc_max);
-    const int ner = P.ne ? min(max(P.ne[b], 0), P.ne_max) : 0;
-    const double x0v0 = x0[0], x0v1 = x0[1];
-    const double g0 = gptr(P.goal)[2 * b], g1 = gptr(P.goal)[2 * b + 1];
-    double xb[5];
-#pragma unroll
-    for (int c = 0; c < 5; ++c) xb[c] = x0[c];
-    bool fin = au_finite(g0) && au_finite(g1);
-#pragma unroll
-    for (int c = 0; c < 5; ++c) fin = fin && au_finite(xb[c]);
-    // obstacles: the eval layout's select_obs compaction (eval_group_one's) and, unfiltered, the audited list
-    int ncs = 0, nes = 0;
+    ncs = 0;
+    nes = 0;
     for (int base = 0; base < P.nc_max; base += GLANES) {
         const int j = base + t;
         const bool valid = j < ncr;
@@ -179,11 +166,13 @@ __device__ __forceinline__ void audit_group_one(const AuP& A, const AWS<N>& w, c
         if (valid) {
             const gdouble* c = gptr(P.cir) + ((size_t)b * P.nc_max + j) * 3;
             c0 = c[0]; c1 = c[1]; c2 = c[2];
-            double* o = w.ao + AU_OBS * j;
-            o[0] = c0; o[1] = c1;
-            o[6] = c2;
+            if (AO) {
+                double* o = w.ao + AU_OBS * j;
+                o[0] = c0; o[1] = c1;
+                o[6] = c2;
+            }
         }
-        const double d = (x0v0 - c0) * (x0v0 - c0) + (x0v1 - c1) * (x0v1 - c1) - c2 * c2;
+        const double d = (px - c0) * (px - c0) + (py - c1) * (py - c1) - c2 * c2;
         const bool keep = valid && (!P.select_obs || d <= P.detect_r2);
         const unsigned m = gballot(keep);
         const int pos = ncs + __builtin_popcount(m & ((1u << t) - 1u));
@@ -203,14 +192,16 @@ __device__ __forceinline__ void audit_group_one(const AuP& A, const AWS<N>& w, c
             const gdouble* ep = gptr(P.elp) + ((size_t)b * P.ne_max + j) * 5;
             for (int i = 0; i < 5; ++i) e[i] = ep[i];
             sincos(e[4], &se, &ce);
-            double* o = w.ao + AU_OBS * (ncr + j);
-            o[0] = e[0]; o[1] = e[1]; o[2] = ce; o[3] = se;
-            o[4] = 1.0 / e[2];
-            o[5] = 1.0 / e[3];
-            o[6] = fmin(e[2], e[3]);
+            if (AO) {
+                double* o = w.ao + AU_OBS * (ncr + j);
+                o[0] = e[0]; o[1] = e[1]; o[2] = ce; o[3] = se;
+                o[4] = 1.0 / e[2];
+                o[5] = 1.0 / e[3];
+                o[6] = fmin(e[2], e[3]);
+            }
         }
         const double rmax = e[2] > e[3] ? e[2] : e[3];
-        const double d = (x0v0 - e[0]) * (x0v0 - e[0]) + (x0v1 - e[1]) * (x0v1 - e[1]) - rmax * rmax;
+        const double d = (px - e[0]) * (px - e[0]) + (py - e[1]) * (py - e[1]) - rmax * rmax;
         const bool keep = valid && (!P.select_obs || d <= P.detect_r2);
         const unsigned m = gballot(keep);
         const int pos = nes + __builtin_popcount(m & ((1u << t) - 1u));
@@ -225,15 +216,17 @@ __device__ __forceinline__ void audit_group_one(const AuP& A, const AWS<N>& w, c
         }
         nes += __builtin_popcount(m);
     }
-    // the plan
-    for (int j = t; j < nu; j += GLANES) {
-        const double v = gptr(P.u0)[(size_t)b * nu + j];
-        w.uv[j] = v;
-        fin = fin && au_finite(v);
-    }
-    fin = gballot(!fin) == 0u;
-    if (t < 5) w.xs[t] = xb[t];
-    wave_sync();
+}
+
+// The violation pass, shared by audit_kernel and the scheduled loop's guard (cl_guard_kernel), in two parts (the audit
+// runs its trace recurrence between them, as it always did).  audit_V: V = E x + G u into w.V from xb and w.uv (in LDS,
+// visible to the group).  audit_viol, after a wave_sync: the headings' sincos, one pass per row family over w.obs (ncs,
+// nes selected), the row reduction — the largest max(cl - c, c - cu, 0) and its row, in every lane of the group.
+template <int N>
+__device__ __forceinline__ void audit_V(const AWS<N>& w, const double* G, const double* E, const double* xb, int t)
+{
+    using D = Dim<N>;
+    constexpr int nu = D::nu, NCP = D::NCPU, NG = D::NG;
     // V = E x0 + G u (eval_group_one's sums)
     for (int g = t; g < NG; g += GLANES) {
         double v = 0.0;
@@ -244,6 +237,65 @@ __device__ __forceinline__ void audit_group_one(const AuP& A, const AWS<N>& w, c
         for (int j = 0; j < nu; ++j) v += gr[j] * w.uv[j];
         w.V[g] = v;
     }
+}
+template <int N>
+__device__ __forceinline__ void audit_viol(const KP& P, const AWS<N>& w, int t, int legv, int ncs, int nes, double& vmax,
+                                           int& vrow)
+{
+    // state pass: lanes 1..N own cos / sin of theta_k
+    if (t >= 1 && t <= N) {
+        double s_, c_;
+        lsincos(w.V[gx(t, 4)], &s_, &c_);
+        w.CT[t] = c_;
+        w.ST[t] = s_;
+    }
+    wave_sync();
+    // the eval rows
+    vmax = 0.0;
+    vrow = 0x7fffffff;
+    {
+        const int nc = P.nc_max, ne = P.ne_max, lo = 2 + nc + ne;
+        audit_rows<N, R_VBX>(P, w, t, legv, 0, 1, 0, vmax, vrow);
+        audit_rows<N, R_VBY>(P, w, t, legv, 0, 1, 1, vmax, vrow);
+        if (nc) audit_rows<N, R_CIR>(P, w, t, legv, ncs, nc, 2, vmax, vrow);
+        if (ne) audit_rows<N, R_ELP>(P, w, t, legv, nes, ne, 2 + nc, vmax, vrow);
+        audit_rows<N, R_LEG>(P, w, t, legv, 0, 1, lo, vmax, vrow);
+        audit_rows<N, R_DTH>(P, w, t, legv, 0, 1, lo + 1, vmax, vrow);
+        if (P.rps > lo + 2) audit_rows<N, R_FEN>(P, w, t, legv, 0, 1, lo + 2, vmax, vrow);
+    }
+    au_reduce16<true>(vmax, vrow);
+}
+
+template <int N>
+__device__ __forceinline__ void audit_group_one(const AuP& A, const AWS<N>& w, const double* G, const double* E,
+                                                const double* tab, unsigned* cnt, long long b, int t)
+{
+    constexpr int nu = Dim<N>::nu;
+    const KP& P = A.kp;
+    const gdouble* x0 = gptr(P.x0) + 5 * b;
+    const int legv = P.leg[b];
+    const int ncr = min(max(P.nc[b], 0), P.nc_max);
+    const int ner = P.ne ? min(max(P.ne[b], 0), P.ne_max) : 0;
+    const double x0v0 = x0[0], x0v1 = x0[1];
+    const double g0 = gptr(P.goal)[2 * b], g1 = gptr(P.goal)[2 * b + 1];
+    double xb[5];
+#pragma unroll
+    for (int c = 0; c < 5; ++c) xb[c] = x0[c];
+    bool fin = au_finite(g0) && au_finite(g1);
+#pragma unroll
+    for (int c = 0; c < 5; ++c) fin = fin && au_finite(xb[c]);
+    int ncs, nes;
+    audit_select<N, true>(P, w, b, t, x0v0, x0v1, ncr, ner, ncs, nes);
+    // the plan
+    for (int j = t; j < nu; j += GLANES) {
+        const double v = gptr(P.u0)[(size_t)b * nu + j];
+        w.uv[j] = v;
+        fin = fin && au_finite(v);
+    }
+    fin = gballot(!fin) == 0u;
+    if (t < 5) w.xs[t] = xb[t];
+    wave_sync();
+    audit_V<N>(w, G, E, xb, t);
     // the trace's recurrence (trace_kernel's sums): lanes 0..4 x_{k+1}[t], lanes 5, 6 p_k[t - 5]
     for (int k = 0; k < N; ++k) {
         const double* x = w.xs + 5 * k;
@@ -264,28 +316,10 @@ __device__ __forceinline__ void audit_group_one(const AuP& A, const AWS<N>& w, c
         }
         wave_sync();
     }
-    // state pass: lanes 1..N own cos / sin of theta_k
-    if (t >= 1 && t <= N) {
-        double s_, c_;
-        lsincos(w.V[gx(t, 4)], &s_, &c_);
-        w.CT[t] = c_;
-        w.ST[t] = s_;
-    }
-    wave_sync();
     // ---- viol: the eval rows
-    double vmax = 0.0;
-    int vrow = 0x7fffffff;
-    {
-        const int nc = P.nc_max, ne = P.ne_max, lo = 2 + nc + ne;
-        audit_rows<N, R_VBX>(P, w, t, legv, 0, 1, 0, vmax, vrow);
-        audit_rows<N, R_VBY>(P, w, t, legv, 0, 1, 1, vmax, vrow);
-        if (nc) audit_rows<N, R_CIR>(P, w, t, legv, ncs, nc, 2, vmax, vrow);
-        if (ne) audit_rows<N, R_ELP>(P, w, t, legv, nes, ne, 2 + nc, vmax, vrow);
-        audit_rows<N, R_LEG>(P, w, t, legv, 0, 1, lo, vmax, vrow);
-        audit_rows<N, R_DTH>(P, w, t, legv, 0, 1, lo + 1, vmax, vrow);
-        if (P.rps > lo + 2) audit_rows<N, R_FEN>(P, w, t, legv, 0, 1, lo + 2, vmax, vrow);
-    }
-    au_reduce16<true>(vmax, vrow);
+    double vmax;
+    int vrow;
+    audit_viol<N>(P, w, t, legv, ncs, nes, vmax, vrow);
     // ---- clear: trace rows x obstacles
     const int rows = A.rows, nobs = ncr + ner, total = N * rows;
     double cmin = INFINITY, kmin = INFINITY;
@@ -437,6 +471,138 @@ static hipError_t launch_audit(int N, const AuP& A, hipStream_t st)
     case 4: return launch_audit_t<4>(A, st);
     case 5: return launch_audit_t<5>(A, st);
     case 6: return launch_audit_t<6>(A, st);
+    }
+    return hipErrorInvalidValue;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The guard of the scheduled closed loop's first-order ticks (cfg.cl_between = ALIPMPC_CL_BETWEEN_GUARDED, alipmpc.hip:
+// cl_between_run_kernel).  Before a first-order tick commands u_fo = ua + du[:, 0:5] (x_nex - xa), this kernel holds it
+// against the eval hook's rows at the tick's own x_nex — alipmpc_audit_batch's column 0 of (x0 = x_nex, u = u_fo,
+// leg = -leg_ind), obstacle selection at x_nex included — and sets CL_FLAG_FIRED where !(viol <= tol): that episode
+// re-solves on this tick instead (host_api.inc).  The audit's mapping: one episode per 16-lane row, 16 per workgroup,
+// grid-stride, the workspace of a group in LDS (AWS without the clearance pass's parts); episodes that have stopped or
+// have no anchor are skipped.  x_nex is formed by every lane of the row (cl_flow, the tick kernels' expression), u_fo by
+// the lane that owns the component (cl_first_order_plan's sum).  A plan or state that is not finite has viol = NaN, as
+// in the audit, and so fires at any tolerance.
+// ------------------------------------------------------------------------------------------------
+struct CLG {
+    KP kp;                // the eval hook's parameters of the episode group (goal, cir, nc, elp, ne; x0, leg, u0 unread)
+    uint8_t* flags;       // CLP::flags
+    const double* x;      // B x 5 plant state
+    const double* pst;    // B x 2 stance foot
+    const double* hdv;    // B x 4 (hd_input_pr at 1)
+    const int8_t* leg;    // B leg_ind
+    const double* xa;     // the anchors (CLB)
+    const double* ua;
+    const double* du;
+    double ch, shb, bsh, tt;   // the rest flow of this tick index (CLN::rest)
+    double tol;
+};
+constexpr int CLG_DOUBLES = (int)((sizeof(CLG) + 15) / 16 * 2);
+
+template <int N>
+__host__ __device__ constexpr int cgws_doubles(int nc_max, int ne_max)
+{
+    const int d = Dim<N>::NG + 2 * (N + 1) + Dim<N>::nu + 3 * nc_max + 9 * ne_max;
+    return d + ((4 - d) % 16 + 16) % 16;   // group stride 4 (mod 16) doubles, as aws_doubles
+}
+template <int N>
+__host__ __device__ constexpr size_t guard_smem(int nc_max, int ne_max)
+{
+    return sizeof(double) * ((size_t)Dim<N>::NG * Dim<N>::NCPU + Dim<N>::NG * 5 + ((Dim<N>::NG * 5) & 1) + CLG_DOUBLES +
+                             (size_t)GROUPS_PER_BLOCK * cgws_doubles<N>(nc_max, ne_max));
+}
+
+template <int N>
+__global__ __launch_bounds__(256) void cl_guard_kernel(CLG Qv)
+{
+    using D = Dim<N>;
+    constexpr int nu = D::nu, NCP = D::NCPU, NG = D::NG;
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    CLG* Qs = reinterpret_cast<CLG*>(smem);   // (the parameters in LDS, as audit_kernel keeps them)
+    double* G = smem + CLG_DOUBLES;
+    double* E = G + NG * NCP;
+    double* wsb = E + NG * 5 + ((NG * 5) & 1);
+    if (threadIdx.x == 0) *Qs = Qv;
+    for (int i = threadIdx.x; i < NG * NCP; i += blockDim.x) G[i] = Qv.kp.G[i];
+    for (int i = threadIdx.x; i < NG * 5; i += blockDim.x) E[i] = Qv.kp.E[i];
+    __syncthreads();
+    const CLG& Q = *Qs;
+    const KP& P = Q.kp;
+    const int gi = threadIdx.x / GLANES, t = threadIdx.x & (GLANES - 1);
+    AWS<N> w;
+    {
+        double* p = wsb + (size_t)gi * cgws_doubles<N>(P.nc_max, P.ne_max);
+        w.V = p; p += NG;
+        w.CT = p; p += N + 1;
+        w.ST = p; p += N + 1;
+        w.uv = p; p += nu;
+        w.obs = p;
+        w.ao = w.xs = w.ps = nullptr;   // (the clearance pass's: not carved here)
+    }
+    for (long long b0 = (long long)blockIdx.x * GROUPS_PER_BLOCK; b0 < P.B; b0 += (long long)gridDim.x * GROUPS_PER_BLOCK) {
+        const long long b = b0 + gi;
+        if (b >= P.B) continue;
+        const uint8_t fl = Q.flags[b];
+        if (!(fl & 1) || !(fl & CL_FLAG_ANCHOR)) continue;
+        double x[5], xn[5];
+#pragma unroll
+        for (int c = 0; c < 5; ++c) x[c] = gptr(Q.x)[5 * b + c];
+        cl_flow(x, gptr(Q.pst)[2 * b], gptr(Q.pst)[2 * b + 1], gptr(Q.hdv)[4 * b + 1], Q.ch, Q.shb, Q.bsh, Q.tt, xn);
+        const int legv = -(int)Q.leg[b];
+        const int ncr = min(max(P.nc[b], 0), P.nc_max);
+        const int ner = P.ne ? min(max(P.ne[b], 0), P.ne_max) : 0;
+        bool fin = au_finite(gptr(P.goal)[2 * b]) && au_finite(gptr(P.goal)[2 * b + 1]);
+        double d[5];
+#pragma unroll
+        for (int c = 0; c < 5; ++c) {
+            fin = fin && au_finite(xn[c]);
+            d[c] = xn[c] - gptr(Q.xa)[5 * b + c];
+        }
+        int ncs, nes;
+        audit_select<N, false>(P, w, b, t, xn[0], xn[1], ncr, ner, ncs, nes);
+        for (int j = t; j < nu; j += GLANES) {
+            const gdouble* r = gptr(Q.du) + ((size_t)b * nu + j) * 7;
+            double v = 0.0;
+            for (int c = 0; c < 5; ++c) v += r[c] * d[c];
+            const double uj = gptr(Q.ua)[(size_t)b * nu + j] + v;
+            w.uv[j] = uj;
+            fin = fin && au_finite(uj);
+        }
+        fin = gballot(!fin) == 0u;
+        wave_sync();
+        audit_V<N>(w, G, E, xn, t);
+        wave_sync();
+        double vmax;
+        int vrow;
+        audit_viol<N>(P, w, t, legv, ncs, nes, vmax, vrow);
+        const bool fire = !(fin && vmax <= Q.tol);
+        if (t == 0 && fire) Q.flags[b] = fl | CL_FLAG_FIRED;
+        wave_sync();
+    }
+}
+
+template <int N>
+static hipError_t launch_guard_t(const CLG& Q, hipStream_t st)
+{
+    const size_t smem = guard_smem<N>(Q.kp.nc_max, Q.kp.ne_max);
+    set_smem((const void*)cl_guard_kernel<N>, smem);
+    const unsigned need = (unsigned)((Q.kp.B + GROUPS_PER_BLOCK - 1) / GROUPS_PER_BLOCK);
+    const unsigned res = resident_blocks((const void*)cl_guard_kernel<N>, smem);
+    const unsigned grid = res > 0 && res < need ? res : (need > 0 ? need : 1u);
+    hipLaunchKernelGGL(cl_guard_kernel<N>, dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), smem, st, Q);
+    return hipGetLastError();
+}
+
+static hipError_t launch_guard(int N, const CLG& Q, hipStream_t st)
+{
+    switch (N) {
+    case 1: return launch_guard_t<1>(Q, st);
+    case 2: return launch_guard_t<2>(Q, st);
+    case 3: return launch_guard_t<3>(Q, st);
+    case 4: return launch_guard_t<4>(Q, st);
+    case 5: return launch_guard_t<5>(Q, st);
     }
     return hipErrorInvalidValue;
 }

@@ -798,10 +798,11 @@ int alipmpc_create(const alipmpc_cfg* cfg, int device, void** handle)
     if (cfg->variant != ALIPMPC_VARIANT_MODI && cfg->variant != ALIPMPC_VARIANT_SIG_STEP &&
         cfg->variant != ALIPMPC_VARIANT_DD)
         return ALIPMPC_EINVAL;
-    if (cfg->cl_between != ALIPMPC_CL_BETWEEN_NOMINAL && cfg->cl_between != ALIPMPC_CL_BETWEEN_FIRST_ORDER)
+    if (cfg->cl_between != ALIPMPC_CL_BETWEEN_NOMINAL && cfg->cl_between != ALIPMPC_CL_BETWEEN_FIRST_ORDER &&
+        cfg->cl_between != ALIPMPC_CL_BETWEEN_GUARDED)
         return ALIPMPC_EINVAL;
-    // first-order ticks read the sensitivity build's du: alipmpc_solve_sens_batch's domain
-    if (cfg->cl_between == ALIPMPC_CL_BETWEEN_FIRST_ORDER &&
+    // first-order ticks (guarded or not) read the sensitivity build's du: alipmpc_solve_sens_batch's domain
+    if (cfg->cl_between != ALIPMPC_CL_BETWEEN_NOMINAL &&
         (cfg->variant == ALIPMPC_VARIANT_DD || cfg->precision == ALIPMPC_PREC_FP32 ||
          cfg->program == ALIPMPC_PROGRAM_LANE || cfg->N > 5))
         return ALIPMPC_EUNSUPPORTED;
@@ -1342,7 +1343,8 @@ static int closed_loop_impl(Handle* h, int64_t B, int32_t S, int32_t f_cyc, doub
     }
     // first-order ticks (cfg.cl_between, a scheduled loop only): each episode's anchor, and the other two outputs of
     // the sensitivity build (a host-pointer schedule registers 32 slots, + 5: within Staging::MAX_SLOTS)
-    const bool fo_mode = sch && cf.cl_between == ALIPMPC_CL_BETWEEN_FIRST_ORDER;
+    const bool guarded = sch && cf.cl_between == ALIPMPC_CL_BETWEEN_GUARDED;   // (mode 1 with the guard, below)
+    const bool fo_mode = (sch && cf.cl_between == ALIPMPC_CL_BETWEEN_FIRST_ORDER) || guarded;
     struct {
         double *xa, *ua, *du, *dfoot;
         int32_t* ok;
@@ -1460,6 +1462,19 @@ static int closed_loop_impl(Handle* h, int64_t B, int32_t S, int32_t f_cyc, doub
         std::memcpy(Qb.MA, am.MA, sizeof(Qb.MA));
         std::memcpy(Qb.MB, am.MB, sizeof(Qb.MB));
     }
+    // guarded mode: the guard's bar (ALIPMPC_CL_GUARD_TOL: development, read per call) and its arguments — the eval
+    // hook's parameters on the scene the solves read
+    CLG Qg;
+    if (guarded) {
+        std::memset(&Qg, 0, sizeof(Qg));
+        Qg.tol = ALIPMPC_CL_GUARD_VIOL;
+        if (const char* ge = std::getenv("ALIPMPC_CL_GUARD_TOL")) {
+            char* end = nullptr;
+            const double v = std::strtod(ge, &end);
+            if (end != ge && *end == '\0' && !std::isnan(v)) Qg.tol = v;
+        }
+        Qg.kp = make_kp(h, B, false);
+    }
     auto solves = [&](int i) { return !sch || ((sch->mask >> i) & 1ull) != 0; };
     // first-order mode: does a tick of the step after tick i not solve (then tick i's solve leaves an anchor)
     auto anchors = [&](int i) {
@@ -1471,6 +1486,64 @@ static int closed_loop_impl(Handle* h, int64_t B, int32_t S, int32_t f_cyc, doub
     const long long TT = (long long)S * f_cyc;
     for (long long t = 0; t < TT;) {
         const int s = (int)(t / f_cyc), i = (int)(t % f_cyc);
+        if (guarded && !solves(i) && live_step == s) {
+            // Guarded mode, after a solve of this step left anchors: one tick at a time, so that no episode runs two
+            // ticks' worth.  The episodes without an anchor run the nominal tick; the guard marks the anchored episodes
+            // whose u_fo fails the rows; the first-order kernel skips those; the solve tick's launches then act on them
+            // alone (cl_anchor_kernel clears the mark).  Every launch is issued whether or not an episode fired.
+            const double rest = T - i * (T / f_cyc);
+            const bool anchor = anchors(i);
+            for (int g = 0; g < G; ++g) {
+                CLP& Cg = grp[g].C;
+                const hipStream_t sg = grp[g].s;
+                Qn.C = Cg;
+                Qn.t0 = t;
+                Qn.nt = 1;
+                Qn.skip_anchored = 1;
+                Qn.plan_traj = grp[g].plan_traj;
+                hipLaunchKernelGGL(cl_nominal_run_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Qn);
+                HIPCHK(h, hipGetLastError());
+                const KP& Pg = grp[g].P;
+                Qg.kp.B = Cg.B;
+                Qg.kp.goal = Pg.goal; Qg.kp.cir = Pg.cir; Qg.kp.nc = Pg.nc; Qg.kp.elp = Pg.elp; Qg.kp.ne = Pg.ne;
+                Qg.flags = Cg.flags; Qg.x = Cg.x; Qg.pst = Cg.pst; Qg.hdv = Cg.hdv; Qg.leg = Cg.leg;
+                Qg.xa = grp[g].xa; Qg.ua = grp[g].ua; Qg.du = grp[g].du;
+                Qg.ch = Qn.rest[i][0]; Qg.shb = Qn.rest[i][1]; Qg.bsh = Qn.rest[i][2]; Qg.tt = Qn.rest[i][3];
+                HIPCHK(h, launch_guard(N, Qg, sg));
+                Qb.Q = Qn;
+                Qb.xa = grp[g].xa; Qb.ua = grp[g].ua; Qb.du = grp[g].du;
+                hipLaunchKernelGGL(cl_between_run_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Qb);
+                HIPCHK(h, hipGetLastError());
+                // the fired episodes' solve tick: the sensitivity build's launch on the group's queue pair
+                Cg.s = s;
+                Cg.i = i;
+                Cg.ch_r = std::cosh(beta * rest); Cg.shb_r = std::sinh(beta * rest) / beta;
+                Cg.bsh_r = std::sinh(beta * rest) * beta; Cg.tr = rest * (1.0 / T);
+                hipLaunchKernelGGL(cl_project_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Cg, 1);
+                HIPCHK(h, hipGetLastError());
+                KP Ps = Pg;
+                Ps.order = nullptr;
+                Ps.queue = h->dq + 2 * (Handle::NQ + g);
+                Ps.grad_out = grp[g].dfoot;
+                Ps.J_out = grp[g].du;
+                Ps.active_out = reinterpret_cast<int8_t*>(grp[g].ok);
+                HIPCHK(h, launch_sens(h, Ps, sg));
+                hipLaunchKernelGGL(cl_update_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Cg, 1);
+                HIPCHK(h, hipGetLastError());
+                if (grp[g].plan_traj) {
+                    hipLaunchKernelGGL(cl_plan_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Cg, grp[g].plan_traj, 1);
+                    HIPCHK(h, hipGetLastError());
+                }
+                CLA A;
+                std::memset(&A, 0, sizeof(A));
+                A.B = Cg.B; A.n = n; A.have = anchor ? 1 : 0; A.active = Cg.active; A.flags = Cg.flags;
+                A.xs = Cg.xs; A.u = Cg.u; A.ok = grp[g].ok; A.xa = grp[g].xa; A.ua = grp[g].ua;
+                hipLaunchKernelGGL(cl_anchor_kernel, dim3(grp[g].g1), dim3(256), 0, sg, A);
+                HIPCHK(h, hipGetLastError());
+            }
+            ++t;
+            continue;
+        }
         if (!solves(i)) {   // a run of nominal ticks, possibly across step boundaries: one launch per group
             // First-order mode, after a solve of this step left anchors: the run ends with the step (the anchor bits
             // change there), its anchored episodes run cl_between_run_kernel and cl_nominal_run_kernel skips them.
@@ -1510,7 +1583,7 @@ static int closed_loop_impl(Handle* h, int64_t B, int32_t S, int32_t f_cyc, doub
                 Cg.i = i;
                 Cg.ch_r = std::cosh(beta * rest); Cg.shb_r = std::sinh(beta * rest) / beta;
                 Cg.bsh_r = std::sinh(beta * rest) * beta; Cg.tr = rest * (1.0 / T);
-                hipLaunchKernelGGL(cl_project_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Cg);
+                hipLaunchKernelGGL(cl_project_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Cg, 0);
                 HIPCHK(h, hipGetLastError());
                 // wave program: after the first tick, solve last tick's long instances first (same bits per instance)
                 Pg.order = nullptr;
@@ -1544,10 +1617,10 @@ static int closed_loop_impl(Handle* h, int64_t B, int32_t S, int32_t f_cyc, doub
                 } else {
                     HIPCHK(h, launch_solve(h, Pg, sg, h->cl_split_it, h->cl_split_tr));
                 }
-                hipLaunchKernelGGL(cl_update_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Cg);
+                hipLaunchKernelGGL(cl_update_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Cg, 0);
                 HIPCHK(h, hipGetLastError());
                 if (grp[g].plan_traj) {
-                    hipLaunchKernelGGL(cl_plan_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Cg, grp[g].plan_traj);
+                    hipLaunchKernelGGL(cl_plan_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Cg, grp[g].plan_traj, 0);
                     HIPCHK(h, hipGetLastError());
                 }
                 if (anchor || live_step == s) {   // (a live anchor bit is cleared by the step's first tick without one)
