@@ -1880,56 +1880,57 @@ __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, lo
     if constexpr (RS) {
         if (rpend) {
             // IPOPT's restoration phase from the failed point (the current iterate, slacks and multipliers; the
-            // augmented filter; theta_R), resto_wave.inc; its iterate comes back through the workspace
+            // augmented filter; theta_R), resto_wave.inc.  It works on this function's own row registers — a failed
+            // search leaves rv, ra0, ra1, cr, sr, zl, zu at the failed point, and a phase-2 record carries them — so
+            // only the iterate goes through the workspace
             rpend = false;
 #ifndef ALIP_NO_SETPRIO
             if (PR && role == 2) __builtin_amdgcn_s_setprio(3);   // (a filler's own restoration: a tail like its owner's)
 #endif
             STAMP(8);
             RELANE();
-#pragma unroll
-            for (int q = 0; q < RPL; ++q) {
-                const int r = lane + WAVE * q;
-                if (r < mo4) {
-                    w.ry[r] = sr[q];
-                    w.rsig[r] = zl[q];
-                    w.rw[r] = zu[q];
-                }
-            }
             if (lane < NG) w.V[lane] = vme;
             wave_sync();
-            const int rr = rfl(resto_wave<N, KSM, R>(wv, fth0, fph0, fth1, fph1, nf, mu, theta_R, it));
+            R lso = R(0.0), fro = R(0.0);
+            const int rr = rfl(resto_wave<N, KSM, R>(wv, fth0, fph0, fth1, fph1, nf, mu, theta_R, it, rtype, rk, roi, rg,
+                                                     cl, cu, rv, ra0, ra1, cr, sr, zl, zu, lso, fro));
             STAMP(25);
             const int rcode = rr & 15;
             it = rr >> 4;
             RELANE();
             vme = lane < NG ? w.V[lane] : R(0.0);
-            R lr = R(0.0);
+            if (rcode == RSW_OK_ORIG) {
+                // the phase ended in its original-problem check: the rows are the accepted trial's at the returned
+                // iterate, and the check's barrier sum and objective there are the regular phase's (the same
+                // expressions on the same point)
+                lsum_cur = lso;
+                f_cur = fro;
+            } else {
+                R lr = R(0.0);
+#pragma unroll
+                for (int q = 0; q < RPL; ++q) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) rv[q][i] = w.V[gen_i(rg[q], i)];
+                    R o[6];
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) o[i] = w.obs6[6 * roi[q] + i];
+                    row_trans(rtype[q], rv[q], w.cst[K_GXG], w.cst[K_GYG], ra0[q], ra1[q]);
+                    cr[q] = row_value(rtype[q], rk[q], rv[q], ra0[q], ra1[q], o, CK);
+                    const R d1 = sr[q] - cl[q], d2 = cu[q] - sr[q];
+                    lr += llog(HL(q) ? (HU(q) ? d1 * d2 : d1) : (HU(q) ? d2 : R(1.0)));
+                }
+                lsum_cur = wsum(lr);
+                f_cur = obj_sum<N, RPL>(cr, mr4);
+            }
 #pragma unroll
             for (int q = 0; q < RPL; ++q) {
-                const int r = lane + WAVE * q;
-                if (r < mo4) {
-                    sr[q] = w.ry[r];
-                    zl[q] = w.rsig[r];
-                    zu[q] = w.rw[r];
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) rv[q][i] = w.V[gen_i(rg[q], i)];
-                R o[6];
-#pragma unroll
-                for (int i = 0; i < 6; ++i) o[i] = w.obs6[6 * roi[q] + i];
-                row_trans(rtype[q], rv[q], w.cst[K_GXG], w.cst[K_GYG], ra0[q], ra1[q]);
-                cr[q] = row_value(rtype[q], rk[q], rv[q], ra0[q], ra1[q], o, CK);
-                const R d1 = sr[q] - cl[q], d2 = cu[q] - sr[q];
-                lr += llog(HL(q) ? (HU(q) ? d1 * d2 : d1) : (HU(q) ? d2 : R(1.0)));
                 // (kappa_sigma safeguard with the regular barrier parameter, as after every iteration)
+                const R d1 = sr[q] - cl[q], d2 = cu[q] - sr[q];
                 idl[q] = HL(q) ? rcp_nr(d1) : R(0.0);
                 idu[q] = HU(q) ? rcp_nr(d2) : R(0.0);
                 zl[q] = HL(q) ? fmin(fmax(zl[q], mu * R(1e-10) * idl[q]), R(1e10) * mu * idl[q]) : R(0.0);
                 zu[q] = HU(q) ? fmin(fmax(zu[q], mu * R(1e-10) * idu[q]), R(1e10) * mu * idu[q]) : R(0.0);
             }
-            lsum_cur = wsum(lr);
-            f_cur = obj_sum<N, RPL>(cr, mr4);
             theta_ok = false;
             wave_sync();
             STAMP(24);
@@ -2224,6 +2225,25 @@ __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, lo
                     for (int j = 0; j < n; ++j) a[j] = (lane < n ? w.K[lane * KLD + j] : R(0.0)) + (lane == j ? dw : R(0.0));
                     a[n] = rhs_l + R(0.0);
                 };
+                if constexpr (RS) {
+                    // the restoration-capable build: one loop, one inlined elimination (dw = 0 first, then the
+                    // correction's sequence; the lean build keeps the form below, its device code is pinned)
+                    R dw = R(0);
+                    for (;;) {
+                        fill(dw);
+                        if (gj_regs<n, R, gj_rb<RPL>>(a, lane)) break;
+                        if (dw == R(0)) {
+                            dw = dw_last == R(0.0) ? R(1e-4) : fmax(R(1e-20), dw_last / R(3.0));
+                        } else {
+                            dw *= dw_last == R(0.0) ? R(100.0) : R(8.0);
+                            if (dw > R(sizeof(R) == 8 ? 1e40 : 1e30)) {   // (not IPOPT's 1e20)
+                                fact_ok = false;
+                                break;
+                            }
+                        }
+                    }
+                    if (dw != R(0)) dw_last = uni(dw);
+                } else {
                 fill(R(0));
                 if (!gj_regs<n, R, gj_rb<RPL>>(a, lane)) {
                     R dw = dw_last == R(0.0) ? R(1e-4) : fmax(R(1e-20), dw_last / R(3.0));
@@ -2237,6 +2257,7 @@ __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, lo
                         }
                     }
                     dw_last = uni(dw);
+                }
                 }
                 xv = lane < n ? a[n] : R(0.0);
             } else if constexpr (GJ) {

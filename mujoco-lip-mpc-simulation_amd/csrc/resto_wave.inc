@@ -18,39 +18,48 @@
 // (augmented with the failed point by the caller) accepts ends the phase.
 //
 // Interface (inlined into the restoration-capable build of solve_one, RS = true, at the top of the iteration after a
-// failed line search; the lean build that phase 1 of a split launch runs never contains it): in — the workspace holds the iterate (w.V), the slacks in w.ry, the
-// slack multipliers zl / zu in w.rsig / w.rw (rows r < mo4); the original filter entries (two per lane), their count,
-// the regular barrier parameter, theta_R and the iteration count.  Out — the same LDS slots hold the new iterate,
-// slacks and multipliers; the return value is (it << 4) | code:
-//   RS_OK          back to the regular phase (multipliers: the complementarity Newton step over the restoration's whole
-//                  slack change, reset to 1 above bound_mult_reset_threshold = 1000)
+// failed line search; the lean build that phase 1 of a split launch runs never contains it): in — the workspace holds
+// the iterate (w.V); the caller's row registers, by reference, hold everything else at the failed point: the row
+// descriptors and bounds, the rows' generator values, sin / cos and values, the slacks and the slack multipliers
+// zl / zu (nothing is decoded or evaluated again here, and nothing but the iterate goes through LDS); the original
+// filter entries (two per lane), their count, the regular barrier parameter, theta_R and the iteration count.  Out —
+// w.V holds the new iterate, the same registers the rows, slacks and multipliers at it; the return value is
+// (it << 4) | code:
+//   RS_OK_ORIG     back to the regular phase through the original-problem check (multipliers: the complementarity
+//                  Newton step over the restoration's whole slack change, reset to 1 above bound_mult_reset_threshold
+//                  = 1000).  The row values are the accepted trial's at the returned iterate, and lsum_o / f_o the
+//                  barrier sum and objective the check computed there: the caller evaluates nothing again
+//   RS_OK          back to the regular phase from a converged restoration problem whose original violation is below
+//                  1e-4 (the caller re-evaluates the rows, as for the codes below)
 //   RS_INFEASIBLE  the restoration problem converged (error <= tol) with the original violation above 1e-4: IPOPT's
 //                  Infeasible_Problem_Detected (status 2), the restoration iterate returned
 //   RS_MAXITER     the iteration cap inside the phase (its current iterate returned)
 //   RS_FAILED      the restoration's own factorisation or line search failed (status 2)
-enum { RSW_OK = 0, RSW_INFEASIBLE = 1, RSW_MAXITER = 2, RSW_FAILED = 3 };
+enum { RSW_OK = 0, RSW_INFEASIBLE = 1, RSW_MAXITER = 2, RSW_FAILED = 3, RSW_OK_ORIG = 4 };
 
-template <int N, int KSM, class R>
-__device__ __forceinline__ int resto_wave(int wv, R fth0, R fph0, R fth1, R fph1, int nfo, R mu_o, R theta_R, int it)
+template <int N, int KSM, class R, int RPL>
+__device__ __forceinline__ int resto_wave(int wv, R fth0, R fph0, R fth1, R fph1, int nfo, R mu_o, R theta_R, int it,
+                                          int (&rtype)[RPL], int (&rk)[RPL], int (&roi)[RPL], uint32_t (&rg)[RPL],
+                                          R (&cl)[RPL], R (&cu)[RPL], R (&rv)[RPL][4], R (&ra0)[RPL], R (&ra1)[RPL],
+                                          R (&cr)[RPL], R (&sr)[RPL], R (&zl0)[RPL], R (&zu0)[RPL], R& lsum_o, R& f_o)
 {
+    static_assert(RPL == (4 * KSM + WAVE - 1) / WAVE, "one row group per 64 rows");
     using D = Dim<N>;
     constexpr int n = D::n;
     constexpr int NT = D::NT;
     constexpr int NCP = D::NCP;
     constexpr int NG = D::NG;
     constexpr int KLD = D::KLD;
-    constexpr int RPL = (4 * KSM + WAVE - 1) / WAVE;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const KP& P = *reinterpret_cast<const KP*>(smem);
     const R* G = reinterpret_cast<const R*>(smem + KP_DOUBLES);
     R* wsb = const_cast<R*>(G) + NG * NCP;
     int lane = lane_id();
     RSTAMP_DECL
-    const int mr4 = rfl(P.mr4), mo4 = rfl(P.mo4), m_max = rfl(P.m_max), rps = rfl(P.rps);
+    const int mr4 = rfl(P.mr4), mo4 = rfl(P.mo4), rps = rfl(P.rps);
     const int nc_max = rfl(P.nc_max), ne_max = rfl(P.ne_max), nobs = nc_max + ne_max;
     const int modi = rfl(P.modi), max_iter = rfl(P.max_iter);
     WSS<N, R> w = carve_s<N, R>(wsb + (size_t)wv * wss_elems<N, R>(nc_max, ne_max, mr4, mo4), nc_max, ne_max, mr4, mo4);
-    const int nc_sel = w.nsel[0], ne_sel = w.nsel[1];
     const R rho = R(1000.0), tol = w.cst[K_TOL];
     const R gth = R(1e-5), gph = R(1e-8), sth = R(1.1), sph = R(2.3), eta = R(1e-8), gal = R(0.05);
     int g4 = lane >> 4, col = lane & 15;
@@ -71,54 +80,23 @@ __device__ __forceinline__ int resto_wave(int wv, R fth0, R fph0, R fth1, R fph1
         }                                                                                                         \
     } while (0)
 #define RCK load_rowk(w.cst)
-    // ---- rows, the restoration's start
-    int rtype[RPL], rk[RPL], roi[RPL];
-    uint32_t rg[RPL];
-    R cl[RPL], cu[RPL], rv[RPL][4], rdv[RPL][4], ra0[RPL], ra1[RPL], cr[RPL];
-    R sr[RPL], vl[RPL], vu[RPL], pp[RPL], nn[RPL], zp[RPL], zn[RPL], yv[RPL], s0[RPL], zl0[RPL], zu0[RPL];
-    R mu = mu_o, nbl = R(0), mal = R(0);
+    // ---- the restoration's start: the rows are the caller's own registers (descriptors, bounds, generator values,
+    // sin / cos, row values, slacks and slack multipliers at the failed point: rows without a constraint carry
+    // s = zl = zu = 0 and infinite bounds there)
+    R rdv[RPL][4];
+    R vl[RPL], vu[RPL], pp[RPL], nn[RPL], zp[RPL], zn[RPL], yv[RPL], s0[RPL];
+    // active rows and bounds are the instance's constants: sum over the active rows of 2 + (cl finite) + (cu finite) =
+    // 2 K_MACT + K_NBL (the caller's counts: small integers, exact)
+    const R mal = w.cst[K_MACT], nbl = R(2) * mal + w.cst[K_NBL];
+    R mu = mu_o;
 #pragma unroll
     for (int q = 0; q < RPL; ++q) {
-        const int r = lane + WAVE * q;
-        RowInfo ri;
-        ri.type = R_NONE; ri.k = 0; ri.slot = 0;
-        if (r < m_max) {
-            ri = decode_row(P, r, nc_sel, ne_sel);
-        } else if (r >= mr4 && r < mr4 + N) {
-            ri.type = R_OBJ;
-            ri.k = r - mr4 + 1;
-        }
-        rtype[q] = ri.type;
-        rk[q] = ri.k;
-        roi[q] = ri.type == R_CIR ? ri.slot : (ri.type == R_ELP ? nc_max + ri.slot : 0);
-        rg[q] = row_gens(ri.type, ri.k);
-        const R clo = r < mr4 ? w.rclo[r] : R(-INFINITY), cuo = r < mr4 ? w.rcuo[r] : R(INFINITY);
-        cl[q] = isfinite(clo) ? clo - R(1e-8) * fmax(R(1.0), fabs(clo)) : -INFINITY;
-        cu[q] = isfinite(cuo) ? cuo + R(1e-8) * fmax(R(1.0), fabs(cuo)) : INFINITY;
-        const bool isc = ri.type < R_NONE;
-        sr[q] = r < mo4 && isc ? w.ry[r] : R(0);
-        zl0[q] = r < mo4 && isc ? w.rsig[r] : R(0);
-        zu0[q] = r < mo4 && isc ? w.rw[r] : R(0);
         s0[q] = sr[q];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            rv[q][i] = w.V[gen_i(rg[q], i)];
-            rdv[q][i] = R(0);
-        }
-        R o[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) o[i] = w.obs6[6 * roi[q] + i];
-        row_trans(rtype[q], rv[q], w.cst[K_GXG], w.cst[K_GYG], ra0[q], ra1[q]);
-        cr[q] = row_value(rtype[q], rk[q], rv[q], ra0[q], ra1[q], o, RCK);
-        if (isc) {
-            mu = fmax(mu, fabs(cr[q] - sr[q]));
-            nbl += R(2) + (R)isfinite(cl[q]) + (R)isfinite(cu[q]);
-            mal += R(1);
-        }
+        for (int i = 0; i < 4; ++i) rdv[q][i] = R(0);
+        if (rtype[q] < R_NONE) mu = fmax(mu, fabs(cr[q] - sr[q]));
     }
     mu = wmax(mu);
-    nbl = wsum(nbl);
-    mal = wsum(mal);
     // x_R and the proximity weights D_j^2 (lane j < n: foothold j = 3k + c at V[gp(k, c)])
     const R xR = lane < n ? w.V[gp(lane / 3, lane % 3)] : R(0);
     const R d2 = lane < n ? R(1) / (fmax(R(1), fabs(xR)) * fmax(R(1), fabs(xR))) : R(0);
@@ -154,21 +132,31 @@ __device__ __forceinline__ int resto_wave(int wv, R fth0, R fph0, R fth1, R fph1
         if (!first) {
             // ---- progress on the ORIGINAL problem (RestoConvergenceCheck): violation reduced to kappa_resto theta_R
             // and acceptable to the original filter with the original barrier function
-            R tho = R(0), lso = R(0);
+            // (the violation decides first: the barrier sum, one log per row, only for an iterate it lets through)
+            R tho = R(0);
 #pragma unroll
-            for (int q = 0; q < RPL; ++q) {
+            for (int q = 0; q < RPL; ++q)
                 if (rtype[q] < R_NONE) tho += fabs(cr[q] - sr[q]);
-                const R d1 = sr[q] - cl[q], d2_ = cu[q] - sr[q];
-                lso += llog(isfinite(cl[q]) ? (isfinite(cu[q]) ? d1 * d2_ : d1) : (isfinite(cu[q]) ? d2_ : R(1.0)));
-            }
-            wsum_pair(tho, lso);
-            const R fo = obj_sum<N, RPL>(cr, mr4);
-            const R pho = fo - mu_o * lso;
-            bool acc = isfinite(pho) && tho <= R(0.9) * theta_R;
+            tho = wsum(tho);
+            bool acc = tho <= R(0.9) * theta_R;
             if (acc) {
-                const bool b0 = lane < nfo && !(tho < fth0 || pho < fph0);
-                const bool b1 = lane + WAVE < nfo && !(tho < fth1 || pho < fph1);
-                acc = __ballot(b0 || b1) == 0ull;
+                R lso = R(0);
+#pragma unroll
+                for (int q = 0; q < RPL; ++q) {
+                    const R d1 = sr[q] - cl[q], d2_ = cu[q] - sr[q];
+                    lso += llog(isfinite(cl[q]) ? (isfinite(cu[q]) ? d1 * d2_ : d1) : (isfinite(cu[q]) ? d2_ : R(1.0)));
+                }
+                lso = wsum(lso);
+                const R fo = obj_sum<N, RPL>(cr, mr4);
+                const R pho = fo - mu_o * lso;
+                lsum_o = lso;
+                f_o = fo;
+                acc = isfinite(pho);
+                if (acc) {
+                    const bool b0 = lane < nfo && !(tho < fth0 || pho < fph0);
+                    const bool b1 = lane + WAVE < nfo && !(tho < fth1 || pho < fph1);
+                    acc = __ballot(b0 || b1) == 0ull;
+                }
             }
             if (acc) {
                 // slack multipliers: the complementarity Newton step over the whole restoration (fraction to the
@@ -200,7 +188,7 @@ __device__ __forceinline__ int resto_wave(int wv, R fth0, R fph0, R fth1, R fph1
                         zu0[q] = rtype[q] < R_NONE && isfinite(cu[q]) ? R(1) : R(0);
                     }
                 }
-                code = RSW_OK;
+                code = RSW_OK_ORIG;
                 break;
             }
         }
@@ -325,22 +313,24 @@ __device__ __forceinline__ int resto_wave(int wv, R fth0, R fph0, R fth1, R fph1
         RSTAMP(3);
         // ---- condensed system weights per row: 1 / D, and the rhs weight y + b / D
         // (reciprocals with one Newton step, rcp_nr, as the regular loop; per row kept for the step pass: the inverse
-        // weights 1 / S_p, 1 / S_n, 1 / S_s, 1 / D and b)
-        R iD[RPL], bv[RPL], iSp[RPL], iSn[RPL], iSs[RPL];
+        // weights 1 / S_p, 1 / S_n, 1 / S_s, 1 / D and b, and the reciprocals 1 / p, 1 / n, 1 / dl, 1 / du)
+        R iD[RPL], bv[RPL], iSp[RPL], iSn[RPL], iSs[RPL], ipv[RPL], inv[RPL], idl_[RPL], idu_[RPL];
 #pragma unroll
         for (int q = 0; q < RPL; ++q) {
             const int r = lane + WAVE * q;
             const bool isc = rtype[q] < R_NONE;
             const R dl = sr[q] - cl[q], du = cu[q] - sr[q];
-            const R ipv = rcp_nr(pp[q]), inv = rcp_nr(nn[q]);
-            const R idl_ = isfinite(cl[q]) ? rcp_nr(dl) : R(0), idu_ = isfinite(cu[q]) ? rcp_nr(du) : R(0);
+            ipv[q] = rcp_nr(pp[q]);
+            inv[q] = rcp_nr(nn[q]);
+            idl_[q] = isfinite(cl[q]) ? rcp_nr(dl) : R(0);
+            idu_[q] = isfinite(cu[q]) ? rcp_nr(du) : R(0);
             iSp[q] = isc ? pp[q] * rcp_nr(zp[q]) : R(0);
             iSn[q] = isc ? nn[q] * rcp_nr(zn[q]) : R(0);
-            iSs[q] = isc ? rcp_nr(vl[q] * idl_ + vu[q] * idu_) : R(0);
-            const R mdl = mu * idl_, mdu = mu * idu_;
+            iSs[q] = isc ? rcp_nr(vl[q] * idl_[q] + vu[q] * idu_[q]) : R(0);
+            const R mdl = mu * idl_[q], mdu = mu * idu_[q];
             const R rc = cr[q] - pp[q] + nn[q] - sr[q];
             iD[q] = isc ? rcp_nr(iSp[q] + iSn[q] + iSs[q]) : R(0);
-            bv[q] = isc ? -rc + (-rho - yv[q] + mu * ipv) * iSp[q] - (-rho + yv[q] + mu * inv) * iSn[q] +
+            bv[q] = isc ? -rc + (-rho - yv[q] + mu * ipv[q]) * iSp[q] - (-rho + yv[q] + mu * inv[q]) * iSn[q] +
                               (-yv[q] + mdl - mdu) * iSs[q]
                         : R(0);
             if (r < mo4) {
@@ -456,21 +446,21 @@ __device__ __forceinline__ int resto_wave(int wv, R fth0, R fph0, R fth1, R fph1
                 for (int j = 0; j < n; ++j) a[j] = (lane < n ? w.K[lane * KLD + j] : R(0)) + (lane == j ? dw : R(0));
                 a[n] = rhs_l + R(0);
             };
-            fill(R(0));
-            bool ok = gj_regs<n, R, gj_rb<RPL>>(a, lane);
-            if (!ok) {
-                R dw = dw_last == R(0) ? R(1e-4) : fmax(R(1e-20), dw_last / R(3));
-                for (;;) {
-                    fill(dw);
-                    if (gj_regs<n, R, gj_rb<RPL>>(a, lane)) {
-                        ok = true;
-                        break;
-                    }
+            // (one loop, one inlined elimination: dw = 0 first, then the correction's sequence)
+            R dw = R(0);
+            bool ok;
+            for (;;) {
+                fill(dw);
+                ok = gj_regs<n, R, gj_rb<RPL>>(a, lane);
+                if (ok) break;
+                if (dw == R(0)) {
+                    dw = dw_last == R(0) ? R(1e-4) : fmax(R(1e-20), dw_last / R(3));
+                } else {
                     dw *= dw_last == R(0) ? R(100) : R(8);
                     if (dw > R(sizeof(R) == 8 ? 1e40 : 1e30)) break;
                 }
-                dw_last = uni(dw);
             }
+            if (dw != R(0)) dw_last = uni(dw);
             if (!ok) {
                 code = RSW_FAILED;
                 break;
@@ -479,24 +469,24 @@ __device__ __forceinline__ int resto_wave(int wv, R fth0, R fph0, R fth1, R fph1
         } else {
             R a[n];
             R myidg = R(1);
+            R dw = R(0);
+            bool ok;
+            for (;;) {
 #pragma unroll
-            for (int j = 0; j < n; ++j) a[j] = lane < n ? w.K[lane * KLD + j] : (lane == j ? R(1) : R(0));
-            bool ok = chol_rows<n>(a, myidg, lane);
-            if (!ok) {
-                R dw = dw_last == R(0) ? R(1e-4) : fmax(R(1e-20), dw_last / R(3));
-                for (;;) {
-#pragma unroll
-                    for (int j = 0; j < n; ++j)
-                        a[j] = (lane < n ? w.K[lane * KLD + j] : (lane == j ? R(1) : R(0))) + (lane == j ? dw : R(0));
-                    if (chol_rows<n>(a, myidg, lane)) {
-                        ok = true;
-                        break;
-                    }
+                for (int j = 0; j < n; ++j) {
+                    const R kv = lane < n ? w.K[lane * KLD + j] : (lane == j ? R(1) : R(0));
+                    a[j] = dw == R(0) ? kv : kv + (lane == j ? dw : R(0));   // (the first try adds nothing, not + 0)
+                }
+                ok = chol_rows<n>(a, myidg, lane);
+                if (ok) break;
+                if (dw == R(0)) {
+                    dw = dw_last == R(0) ? R(1e-4) : fmax(R(1e-20), dw_last / R(3));
+                } else {
                     dw *= dw_last == R(0) ? R(100) : R(8);
                     if (dw > R(sizeof(R) == 8 ? 1e40 : 1e30)) break;
                 }
-                dw_last = uni(dw);
             }
+            if (dw != R(0)) dw_last = uni(dw);
             if (!ok) {
                 code = RSW_FAILED;
                 break;
@@ -552,24 +542,23 @@ __device__ __forceinline__ int resto_wave(int wv, R fth0, R fph0, R fth1, R fph1
             }
             const bool isc = rtype[q] < R_NONE, hl = isc && isfinite(cl[q]), hu = isc && isfinite(cu[q]);
             const R dl = sr[q] - cl[q], du = cu[q] - sr[q];
-            const R ipv = rcp_nr(pp[q]), inv = rcp_nr(nn[q]);
-            const R idl_ = hl ? rcp_nr(dl) : R(0), idu_ = hu ? rcp_nr(du) : R(0);
-            const R mdl = mu * idl_, mdu = mu * idu_;
+            // (1 / p, 1 / n, 1 / dl, 1 / du: the weights pass's, their arguments unchanged since)
+            const R mdl = mu * idl_[q], mdu = mu * idu_[q];
             dy[q] = isc ? (bv[q] - jd) * iD[q] : R(0);
-            dpv[q] = isc ? (-rho - yv[q] + mu * ipv - dy[q]) * iSp[q] : R(0);
-            dnv[q] = isc ? (-rho + yv[q] + mu * inv + dy[q]) * iSn[q] : R(0);
+            dpv[q] = isc ? (-rho - yv[q] + mu * ipv[q] - dy[q]) * iSp[q] : R(0);
+            dnv[q] = isc ? (-rho + yv[q] + mu * inv[q] + dy[q]) * iSn[q] : R(0);
             ds[q] = isc ? (-yv[q] + mdl - mdu - dy[q]) * iSs[q] : R(0);
-            dzp[q] = isc ? mu * ipv - zp[q] - zp[q] * ipv * dpv[q] : R(0);
-            dzn[q] = isc ? mu * inv - zn[q] - zn[q] * inv * dnv[q] : R(0);
-            dvl[q] = hl ? mdl - vl[q] - vl[q] * idl_ * ds[q] : R(0);
-            dvu[q] = hu ? mdu - vu[q] + vu[q] * idu_ * ds[q] : R(0);
+            dzp[q] = isc ? mu * ipv[q] - zp[q] - zp[q] * ipv[q] * dpv[q] : R(0);
+            dzn[q] = isc ? mu * inv[q] - zn[q] - zn[q] * inv[q] * dnv[q] : R(0);
+            dvl[q] = hl ? mdl - vl[q] - vl[q] * idl_[q] * ds[q] : R(0);
+            dvu[q] = hu ? mdu - vu[q] + vu[q] * idu_[q] * ds[q] : R(0);
             if (isc) {
                 if (dpv[q] < R(0)) ap = fmin(ap, -tau * pp[q] * rcp_nr(dpv[q]));
                 if (dnv[q] < R(0)) ap = fmin(ap, -tau * nn[q] * rcp_nr(dnv[q]));
                 if (dzp[q] < R(0)) az = fmin(az, -tau * zp[q] * rcp_nr(dzp[q]));
                 if (dzn[q] < R(0)) az = fmin(az, -tau * zn[q] * rcp_nr(dzn[q]));
                 theta += fabs(cr[q] - pp[q] + nn[q] - sr[q]);
-                gpn += (rho - mu * ipv) * dpv[q] + (rho - mu * inv) * dnv[q] - (mdl - mdu) * ds[q];
+                gpn += (rho - mu * ipv[q]) * dpv[q] + (rho - mu * inv[q]) * dnv[q] - (mdl - mdu) * ds[q];
                 lin += rho * (pp[q] + nn[q]) - mu * llog(pp[q] * nn[q] * (hl ? (hu ? dl * du : dl) : (hu ? du : R(1))));
             }
             const R ids = rcp_nr(ds[q]);
@@ -705,18 +694,7 @@ __device__ __forceinline__ int resto_wave(int wv, R fth0, R fph0, R fth1, R fph1
         ++it;
         RSTAMP(10);
     }
-    // ---- hand the iterate back: slacks and slack multipliers (w.V already holds the iterate)
-    wave_sync();
-#pragma unroll
-    for (int q = 0; q < RPL; ++q) {
-        const int r = lane + WAVE * q;
-        if (r < mo4) {
-            w.ry[r] = sr[q];
-            w.rsig[r] = zl0[q];
-            w.rw[r] = zu0[q];
-        }
-    }
-    wave_sync();
+    // ---- the iterate is in w.V; rows, slacks and slack multipliers are the caller's registers
     RSTAMP(11);
     RSTAMP_FLUSH(it - it_in);
     return (it << 4) | code;
