@@ -242,6 +242,10 @@ int alipmpc_solve_sens_batch(void* handle, int64_t B,
                              double* dfoot, double* du, int32_t* sens_ok,
                              void* hip_stream);
 
+/* The plan's sensitivities to the obstacles (alipmpc_sens_obs_cols, alipmpc_solve_sens_obs_batch) are declared in an
+ * extension header of their own; a translation unit that includes this header has them too. */
+#include "alipmpc_sens_obs.h"
+
 /*
  * Evaluate the NLP callbacks and the set-up at given u (parity / oracle hook).  m_max = N*rows_per_step.
  *   f B, grad B x n, c B x m_max, J B x m_max x n, cl/cu B x m_max, goal_eff B x 2 (after detour),

@@ -91,6 +91,10 @@ def _steps1(d):
     return d["S"] + 1
 
 
+def _obs_cols(d):   # the obstacle columns of solve_sens_obs (alipmpc_sens_obs_cols)
+    return 3 * d["nc_max"] + 5 * d["ne_max"]
+
+
 # x0, goal, leg, cir, nc, elp, ne: the scene block of solve / eval / rollout / audit and, around foot0, the closed loops
 _SCENE = (_in("x0", _f8, "B", "sdim"), _in("goal", _f8, "B", 2, bcast=True),
           _in("leg", _i1, "B", nullable=True, bcast=True), _in("cir", _f8, "B", "nc_max", 3, bcast=True),
@@ -163,6 +167,17 @@ _ABI = {
     "alipmpc_destroy": Entry(None, (_HANDLE,)),
 }
 EXPORTS = tuple(_ABI)
+# The exports of the extension header include/alipmpc_sens_obs.h (which alipmpc.h includes), in the same form: _ABI is
+# alipmpc.h's own table, held against that header entry by entry (tests/test_binding_host.py), this one against its
+# (tests/test_sens_obs_binding_host.py).
+_ABI_EXT = {
+    "alipmpc_sens_obs_cols": Entry(_i32, (_CFG,)),
+    "alipmpc_solve_sens_obs_batch": Entry(_int, (_HANDLE, _B) + _SOLVE_IN + _SOLVE_OUT + (
+        _out("dfoot", _f8, "B", 3, 7), _out("du", _f8, "B", "n", 7), _out("sens_ok", _i4, "B"),
+        _out("dfoot_obs", _f8, "B", 3, _obs_cols, opt=False), _out("du_obs", _f8, "B", "n", _obs_cols), _STREAM)),
+}
+EXPORTS_EXT = tuple(_ABI_EXT)
+_ENTRIES = {**_ABI, **_ABI_EXT}   # every entry point, for the call paths
 
 
 def _shape(a, d):
@@ -216,7 +231,7 @@ def _device_plan(args):
             operator.itemgetter(*(gathered.index(i) for i in range(len(mid)))))
 
 
-_DEVICE_PLAN = {name: _device_plan(e.args) for name, e in _ABI.items() if name.endswith("_batch")}
+_DEVICE_PLAN = {name: _device_plan(e.args) for name, e in _ENTRIES.items() if name.endswith("_batch")}
 
 _lib = None
 
@@ -244,7 +259,7 @@ def load(build_if_missing=True):
     if not os.path.exists(path):
         raise RuntimeError(f"libalipmpc.so not found at {path}; run alipmpc.build.build()")
     L = ctypes.CDLL(path)
-    for name, entry in _ABI.items():
+    for name, entry in _ENTRIES.items():
         if name in _ALWAYS or hasattr(L, name):    # an absent symbol gets no prototype; one of _ALWAYS raises here
             f = getattr(L, name)
             f.argtypes = [a.ctype if isinstance(a, Scalar) else _P for a in entry.args]
@@ -322,7 +337,32 @@ def _ptr(a):
     return _P(data_ptr()) if data_ptr is not None else a.ctypes.data_as(_P)
 
 
-class Solver:
+class _SensObsCalls:
+    """The calls of the extension header include/alipmpc_sens_obs.h (_ABI_EXT), on Solver through this base class: the
+    plan's sensitivities to the obstacles."""
+
+    @property
+    def sens_obs_cols(self):
+        """Obstacle columns of solve_sens_obs: 3 nc_max + 5 ne_max (alipmpc_sens_obs_cols)."""
+        return int(self._L.alipmpc_sens_obs_cols(ctypes.byref(self.cfg)))
+
+    def solve_sens_obs(self, x0, goal, leg, cir, nc, elp=None, ne=None, u0=None, want_du=True, want_state=True):
+        """solve_sens() with the obstacle columns (alipmpc_solve_sens_obs_batch): the dict of solve_sens plus dfoot_obs
+        (B, 3, P) and du_obs (B, 5N, P) (None unless want_du), P = sens_obs_cols — columns as
+        alipmpc.sensitivity.obs_columns(nc_max, ne_max), by the caller's input slots; exact zeros for a slot past the
+        instance's count or dropped by select_obs, NaN rows where the instance's sensitivity is invalid.  want_state =
+        False leaves dfoot, du and sens_ok out (None)."""
+        skip = (() if want_du else ("du", "du_obs")) + (() if want_state else ("dfoot", "du", "sens_ok"))
+        return self._host("alipmpc_solve_sens_obs_batch", self._scene(x0, goal, leg, cir, nc, elp, ne, u0=u0),
+                          skip=skip)
+
+    def solve_sens_obs_device(self, inp, out, stream=None):
+        """Asynchronous solve with sensitivities and their obstacle columns on device tensors: inp as solve_device; out
+        as solve_sens_device (dfoot optional here) plus dfoot_obs (B,3,P) (required) and du_obs (B,5N,P) (optional)."""
+        self._device("alipmpc_solve_sens_obs_batch", inp, out, stream, inp["x0"].shape[0])
+
+
+class Solver(_SensObsCalls):
     """Owns one libalipmpc handle (one config, one device)."""
 
     def __init__(self, cfg, device=0):
@@ -392,7 +432,7 @@ class Solver:
         and returns the outputs as a dict in the table's order.  B is scalars["B"] or the leading size of the
         entry's first array; `dims` adds names for the shape rules (a B there sizes the arrays only).  `given` is the
         caller's own dict: converted arrays replace what it held."""
-        cfg, args = self.cfg, _ABI[name].args
+        cfg, args = self.cfg, _ENTRIES[name].args
         d = dict(n=self.n, sdim=self.sdim, m_max=self.m_max, cfg=cfg, N=cfg.N, nc_max=cfg.nc_max, ne_max=cfg.ne_max,
                  handle=self._h, hip_stream=None)
         d.update(scalars, **dims)
@@ -418,7 +458,7 @@ class Solver:
 
     def _batch_size(self, name, given):
         """B of a host call: the leading size of the entry's first array, which is converted here, once, in `given`."""
-        lead = next(a for a in _ABI[name].args if isinstance(a, Array))
+        lead = next(a for a in _ENTRIES[name].args if isinstance(a, Array))
         x = np.ascontiguousarray(given[lead.key], lead.dtype).reshape(_shape(lead, dict(B=-1, sdim=self.sdim)))
         given[lead.key] = x
         return x.shape[0]

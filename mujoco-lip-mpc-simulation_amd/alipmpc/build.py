@@ -23,6 +23,7 @@ SRC = os.path.join(ROOT, "csrc", "alipmpc.hip")
 # nothing else belongs in csrc/ under that suffix)
 INCS = sorted(glob.glob(os.path.join(ROOT, "csrc", "*.inc")))
 HDR = os.path.join(REPO, "include", "alipmpc.h")
+HDR_EXT = [os.path.join(REPO, "include", "alipmpc_sens_obs.h")]   # extension headers alipmpc.h includes
 LIB = os.path.join(PKG, "libalipmpc.so")
 PARTS = range(0, 9)
 
@@ -40,7 +41,7 @@ def build_id(extra=(), src=None):
     and the extra flags.  Compiled into the library (alipmpc_build_id) so a counter record made with one build is
     never attached to a bench line of another (tools/roofline.py, bench.py)."""
     h = hashlib.sha256()
-    for p in (src or SRC, *INCS, HDR):
+    for p in (src or SRC, *INCS, HDR, *HDR_EXT):
         with open(p, "rb") as fh:
             h.update(fh.read())
     h.update(" ".join([*ARCH, *FLAGS, *extra]).encode())
@@ -51,7 +52,7 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    return any(os.path.getmtime(p) > t for p in (SRC, *INCS, HDR, __file__))
+    return any(os.path.getmtime(p) > t for p in (SRC, *INCS, HDR, *HDR_EXT, __file__))
 
 
 def _run(cmd, verbose):

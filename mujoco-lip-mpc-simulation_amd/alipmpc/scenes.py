@@ -118,6 +118,35 @@ def make_batch(B, seed=0, n_cir=5, n_elp=0, N=3, nc_max=None, ne_max=None, scene
                 u0=u0)
 
 
+def block_path(batch, seed, gap=(0.6, 1.4), lat=0.5):
+    """A copy of `batch` (a make_batch dict) with one obstacle per instance moved into the way to the goal, so that its
+    D-CBF rows are active at the solution (on the random fields they rarely are, and the plan's obstacle sensitivities
+    are zero to rounding).  With d the unit vector from x0's position to the goal and n = (-d_y, d_x), the moved
+    obstacle's centre goes to pos + (R + g_b) d + t_b R n, R = r or max(a, b) (inflated, as stored), g_b ~ U(gap) and
+    t_b ~ U(-lat, lat) drawn from default_rng(1000 + seed), all g first.  Instance b moves ellipse slot
+    (b // 2) % ne[b] if it has ellipses and b is odd, circle slot b % nc[b] otherwise: the rotating slot puts
+    obstacles that select_obs drops in front of the moved one."""
+    bt = {k: (None if v is None else np.array(v)) for k, v in batch.items()}
+    B = bt["x0"].shape[0]
+    rng = np.random.default_rng(1000 + seed)
+    g = rng.uniform(gap[0], gap[1], B)
+    t = rng.uniform(-lat, lat, B)
+    pos = bt["x0"][:, 0:2]
+    d = np.broadcast_to(bt["goal"], (B, 2)) - pos
+    d = d / np.linalg.norm(d, axis=1, keepdims=True)
+    nrm = np.stack([-d[:, 1], d[:, 0]], axis=1)
+    for b in range(B):
+        n_elp = int(bt["ne"][b]) if bt.get("ne") is not None else 0
+        if n_elp > 0 and b % 2 == 1:
+            o = bt["elp"][b, (b // 2) % n_elp]
+            R = max(o[2], o[3])
+        else:
+            o = bt["cir"][b, b % int(bt["nc"][b])]
+            R = o[2]
+        o[0:2] = pos[b] + (R + g[b]) * d[b] + t[b] * R * nrm[b]
+    return bt
+
+
 def make_batch_vec(B, seed=0, n_cir=5, n_elp=0, N=3, fields=None, max_rounds=4000):
     """Same distribution as make_batch, vectorised over instances, with `fields` distinct obstacle fields
     (default: one PER INSTANCE — the Monte-Carlo sweep of BASELINE cfg5, 1M randomized scenes; instance b

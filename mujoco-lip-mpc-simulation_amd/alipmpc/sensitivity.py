@@ -1,5 +1,6 @@
-"""Plan sensitivities (alipmpc_solve_sens_batch, Solver.solve_sens): the column layout, the detour's chain rule in
-numpy, and the first-order update of a plan.
+"""Plan sensitivities (alipmpc_solve_sens_batch, Solver.solve_sens; alipmpc_solve_sens_obs_batch,
+Solver.solve_sens_obs for the obstacle columns): the column layouts, the detour's chain rule in numpy, and the first-order
+update of a plan.
 
 The kernel returns dfoot (B, 3, 7) and du (B, 5N, 7): derivatives of the first foothold and of the canonical plan
 u_k = x_{k+1} with respect to theta = (x0[0..4], goal[0..1]), taken at the accepted iterate with the barrier parameter
@@ -78,9 +79,33 @@ def fold_detour(d_partial, side):
     return d
 
 
-def first_order(u, du, dx0=None, dgoal=None):
-    """First-order update of a plan: u + du[..., 0:5] dx0 + du[..., 5:7] dgoal.  u (B, n) with du (B, n, 7) (a solve's u
-    and du, or foot (B, 3) and dfoot (B, 3, 7)); dx0 (B, 5) or (5,), dgoal (B, 2) or (2,); either may be None (zero).
+def obs_columns(nc_max, ne_max):
+    """Names of the obstacle columns of dfoot_obs / du_obs (alipmpc_solve_sens_obs_batch, Solver.solve_sens_obs), by the
+    caller's input slots: "cir0_cx", "cir0_cy", "cir0_r", ..., then "elp0_cx", "elp0_cy", "elp0_a", "elp0_b",
+    "elp0_phi", ... — 3 nc_max + 5 ne_max of them."""
+    return tuple(f"cir{j}_{p}" for j in range(nc_max) for p in ("cx", "cy", "r")) + \
+        tuple(f"elp{j}_{p}" for j in range(ne_max) for p in ("cx", "cy", "a", "b", "phi"))
+
+
+def obs_col(kind, slot, nc_max):
+    """First column of input slot `slot` of kind "cir" (3 columns: cx, cy, r) or "elp" (5: cx, cy, a, b, phi)."""
+    if kind == "cir":
+        if not 0 <= slot < nc_max:
+            raise ValueError(f"circle slot {slot} outside 0 .. {nc_max - 1}")
+        return 3 * slot
+    if kind == "elp":
+        if slot < 0:
+            raise ValueError(f"ellipse slot {slot}")
+        return 3 * nc_max + 5 * slot
+    raise ValueError(f"kind {kind!r}: 'cir' or 'elp'")
+
+
+def first_order(u, du, dx0=None, dgoal=None, du_obs=None, dcir=None, delp=None):
+    """First-order update of a plan: u + du[..., 0:5] dx0 + du[..., 5:7] dgoal + du_obs [dcir, delp].  u (B, n) with du
+    (B, n, 7) (a solve's u and du, or foot (B, 3) and dfoot (B, 3, 7)); dx0 (B, 5) or (5,), dgoal (B, 2) or (2,); either
+    may be None (zero).  du_obs (B, n, 3 nc_max + 5 ne_max) (solve_sens_obs' du_obs or dfoot_obs) with dcir (B, nc_max, 3)
+    or (nc_max, 3), the change of the circles (cx, cy, r), and delp (B, ne_max, 5) or (ne_max, 5), that of the ellipses
+    (cx, cy, a, b, phi); either may be None (zero), and nc_max is read from dcir (0 without it: no circle slots).
     Rows whose derivative is NaN (sens_ok = 0) come back NaN."""
     u = np.asarray(u, float)
     du = np.asarray(du, float)
@@ -93,4 +118,25 @@ def first_order(u, du, dx0=None, dgoal=None):
     if dgoal is not None:
         out = out + np.einsum("...ij,...j->...i", du[..., COL_GOAL], np.broadcast_to(np.asarray(dgoal, float),
                                                                                     u.shape[:-1] + (2,)))
+    if dcir is not None or delp is not None:
+        if du_obs is None:
+            raise ValueError("dcir / delp need du_obs")
+        du_obs = np.asarray(du_obs, float)
+        if du_obs.shape[:-1] != u.shape:
+            raise ValueError(f"du_obs has shape {du_obs.shape}, {u.shape + ('P',)} expected")
+        ncol = du_obs.shape[-1]
+        if dcir is not None:
+            dcir = np.asarray(dcir, float)
+            nc3 = 3 * dcir.shape[-2]
+            if dcir.shape[-1] != 3 or nc3 > ncol:
+                raise ValueError(f"dcir has shape {dcir.shape} for {ncol} obstacle columns")
+            flat = np.broadcast_to(dcir.reshape(dcir.shape[:-2] + (nc3,)), u.shape[:-1] + (nc3,))
+            out = out + np.einsum("...ij,...j->...i", du_obs[..., :nc3], flat)
+        if delp is not None:
+            delp = np.asarray(delp, float)
+            ne5 = 5 * delp.shape[-2]
+            if delp.shape[-1] != 5 or ne5 > ncol or (dcir is not None and nc3 + ne5 != ncol):
+                raise ValueError(f"delp has shape {delp.shape} for {ncol} obstacle columns")
+            flat = np.broadcast_to(delp.reshape(delp.shape[:-2] + (ne5,)), u.shape[:-1] + (ne5,))
+            out = out + np.einsum("...ij,...j->...i", du_obs[..., ncol - ne5:], flat)
     return out

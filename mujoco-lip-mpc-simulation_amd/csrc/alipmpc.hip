@@ -838,9 +838,11 @@ __device__ __forceinline__ void err_scales(T nz, T den0, T den1, T& sd, T& sc)
 #endif
 }
 
-template <int N, class WT>
+// MAP (the obstacle-sensitivity build only): km[0] / km[1] receive select_obs' keep masks of the circle / ellipse
+// input slots (bit i = input slot i was kept; its selected slot is the number of kept slots below it)
+template <int N, bool MAP = false, class WT>
 __device__ void prologue(const KP& P, const WT& w, const typename WT::real* G, const double* E,
-                         long long b, double& gxg, double& gyg, int& legv, double& uj)
+                         long long b, double& gxg, double& gyg, int& legv, double& uj, uint32_t* km = nullptr)
 {
     using D = Dim<N>;
     const int lane = lane_id();
@@ -868,7 +870,9 @@ __device__ void prologue(const KP& P, const WT& w, const typename WT::real* G, c
             w.obs[3 * pos + 2] = c2;
         }
         if (lane == 0) w.nsel[0] = __builtin_popcountll(m);
+        if constexpr (MAP) km[0] = (uint32_t)m;
     }
+    if constexpr (MAP) km[1] = 0u;
     if (P.ne_max > 0) {
         bool valid = lane < ner && lane < P.ne_max;
         double e[5] = {0, 0, 0, 0, 0};
@@ -893,6 +897,7 @@ __device__ void prologue(const KP& P, const WT& w, const typename WT::real* G, c
             qq[3 * P.ne_max + pos] = (e[3] * e[2]) * (e[3] * e[2]);
         }
         if (lane == 0) w.nsel[1] = __builtin_popcountll(m);
+        if constexpr (MAP) km[1] = (uint32_t)m;
     } else if (lane == 0) {
         w.nsel[1] = 0;
     }
@@ -1254,7 +1259,9 @@ struct RowK {   // uniform constants of the row functions
     R gm1, s, q, p, r, gxg, gyg;
 };
 // cst slots
-enum { K_GM1 = 0, K_S, K_Q, K_P, K_R, K_GXG, K_GYG, K_THMAX, K_THMIN, K_MACT, K_NBL, K_TOL, K_ACCTOL, K_NTR, K_XR };
+enum { K_GM1 = 0, K_S, K_Q, K_P, K_R, K_GXG, K_GYG, K_THMAX, K_THMIN, K_MACT, K_NBL, K_TOL, K_ACCTOL, K_NTR, K_XR,
+       K_SMAP };   // (K_SMAP: the obstacle-sensitivity build's keep masks, as bits; no other build writes the slot)
+static_assert(K_SMAP < 16, "cst holds 16 slots");
 template <class R>
 __device__ __forceinline__ RowK<R> load_rowk(const R* cst)
 {
@@ -1521,8 +1528,10 @@ constexpr bool TEAM_HANDOVER = 3 * WAVE * RPL + 3 <= Dim<N>::NCP * Dim<N>::KLD;
 // for its whole resume; role 2 = a filler wave, whose iteration-based priority stays below the owners' until a
 // restoration of its own.  Without PR the role compiles out.
 // SN: the sensitivity build (sens_kernel, alipmpc_solve_sens_batch): after the outputs of an instance, sens_epilogue
-// (sens_wave.inc) differentiates the plan at the accepted iterate.  Without SN none of it is compiled.
-template <int N, int KSM, class R, bool Q, bool TM = false, bool RS = false, bool PR = false, bool SN = false>
+// (sens_wave.inc) differentiates the plan at the accepted iterate.  Without SN none of it is compiled.  SN = 2
+// (sens_obs_kernel, alipmpc_solve_sens_obs_batch): the epilogue adds the obstacle columns, for which the prologue's
+// keep masks travel to it in w.cst[K_SMAP].
+template <int N, int KSM, class R, bool Q, bool TM = false, bool RS = false, bool PR = false, int SN = 0>
 __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, long long b, long long rec = -1,
                                           int tm = 0, int role = 0)
 {
@@ -1564,7 +1573,11 @@ __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, lo
 
     double gxg, gyg, uj;
     int legv;
-    prologue<N>(P, w, G, P.E, b, gxg, gyg, legv, uj);   // (E from global memory: read once per instance)
+    uint32_t km[2] = {0u, 0u};
+    if constexpr (SN == 2)
+        prologue<N, true>(P, w, G, P.E, b, gxg, gyg, legv, uj, km);
+    else
+        prologue<N>(P, w, G, P.E, b, gxg, gyg, legv, uj);   // (E from global memory: read once per instance)
     const int nc_sel = w.nsel[0], ne_sel = w.nsel[1];
     // unified quadratic forms per obstacle row slot (zero form for unused slots)
     {
@@ -1611,6 +1624,7 @@ __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, lo
         w.cst[K_XR] = R(0.0);
         w.cst[K_GM1] = P.gm1; w.cst[K_S] = P.s; w.cst[K_Q] = P.q; w.cst[K_P] = P.p; w.cst[K_R] = P.r;
         w.cst[K_GXG] = gxg; w.cst[K_GYG] = gyg; w.cst[K_TOL] = P.tol; w.cst[K_ACCTOL] = P.acc_tol;
+        if constexpr (SN == 2) w.cst[K_SMAP] = __longlong_as_double((long long)km[0] | ((long long)km[1] << 32));
     }
     wave_sync();
 #define CK load_rowk(w.cst)
@@ -2772,8 +2786,8 @@ __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, lo
     }
     if constexpr (SN) {
         static_assert(sizeof(R) == 8 && !TM && !PR, "the sensitivity build: fp64, one wave per instance");
-        sens_epilogue<N, KSM, RPL>(P, w, G, b, lane, rfl(status) == 0 || rfl(status) == 1, rtype, rk, roi, rv, ra0, ra1,
-                                   zl, zu, idl, idu, mo4, rps, nobs, modi);
+        sens_epilogue<N, KSM, RPL, SN == 2>(P, w, G, b, lane, rfl(status) == 0 || rfl(status) == 1, rtype, rk, roi, rv,
+                                            ra0, ra1, zl, zu, idl, idu, mo4, rps, nobs, modi);
     }
 #undef RELANE
 #undef CK
@@ -2967,7 +2981,34 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK, (solve_waves<KSM, double, R
         asm volatile("" : "+s"(rec));
         // (the scheduled closed loop's first-order mode: skip finished episodes, as solve_kernel's work queue does; no
         // launch order here)
-        if (!Pv.active || Pv.active[b]) solve_one<N, KSM, double, true, false, RS, false, true>(P, G, wsb, wv, b, rec);
+        if (!Pv.active || Pv.active[b]) solve_one<N, KSM, double, true, false, RS, false, 1>(P, G, wsb, wv, b, rec);
+    }
+    queue_exit(q);
+}
+
+// The obstacle-sensitivity build (alipmpc_solve_sens_obs_batch): sens_kernel's launch form and solve,
+// its epilogue followed by the obstacle columns.  A build of its own, so that sens_kernel, which the closed loop's
+// first-order and guarded ticks launch, keeps its code.
+template <int N, int KSM, bool RS>
+__global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK, (solve_waves<KSM, double, RS>())) void sens_obs_kernel(KP Pv)
+{
+    using D = Dim<N>;
+    constexpr int NCP = D::NCP;
+    constexpr int NG = D::NG;
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    KP* Ps = reinterpret_cast<KP*>(smem);
+    double* G = smem + KP_DOUBLES;
+    double* wsb = G + NG * NCP;
+    if (threadIdx.x == 0) *Ps = Pv;
+    for (int i = threadIdx.x; i < NG * NCP; i += blockDim.x) G[i] = Pv.G[i];
+    __syncthreads();
+    const KP& P = *Ps;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+    uint32_t* const q = Pv.queue;
+    for (long long b = next_instance(q); b < Pv.B; b = next_instance(q)) {
+        long long rec = -1;
+        asm volatile("" : "+s"(rec));
+        solve_one<N, KSM, double, true, false, RS, false, 2>(P, G, wsb, wv, b, rec);
     }
     queue_exit(q);
 }
@@ -5622,7 +5663,7 @@ void launch_solve(const KP& P0, size_t smem, hipStream_t st, unsigned* res_out)
 // the sensitivity build (fp64, N <= 5: n <= 15, the gj_regs domain): the persistent work queue over at most the
 // resident workgroups, whatever B is
 template <int N>
-hipError_t launch_sens_t(const KP& P0, size_t smem, hipStream_t st)
+hipError_t launch_sens_t(const KP& P0, size_t smem, hipStream_t st, bool obs)
 {
     if constexpr (Dim<N>::n > ALIP_GJ_MAX_N || Dim<N>::n > 15) {
         return hipErrorNotSupported;
@@ -5636,7 +5677,11 @@ hipError_t launch_sens_t(const KP& P0, size_t smem, hipStream_t st)
         };
 #define ALIP_GO(K)                                 \
     do {                                           \
-        if (P0.resto_ipopt)                        \
+        if (obs && P0.resto_ipopt)                 \
+            go(sens_obs_kernel<N, K, true>);       \
+        else if (obs)                              \
+            go(sens_obs_kernel<N, K, false>);      \
+        else if (P0.resto_ipopt)                   \
             go(sens_kernel<N, K, true>);           \
         else                                       \
             go(sens_kernel<N, K, false>);          \
@@ -5712,15 +5757,15 @@ hipError_t launch_dd(bool solve, const KP& P, size_t smem, hipStream_t st)
     {                                                                                                  \
         return launch_dd<k>(solve, P, smem, st);                                                       \
     }                                                                                                  \
-    hipError_t launch_sens_##k(const KP& P, size_t smem, hipStream_t st)                               \
+    hipError_t launch_sens_##k(const KP& P, size_t smem, hipStream_t st, bool obs)                     \
     {                                                                                                  \
-        return launch_sens_t<k>(P, smem, st);                                                          \
+        return launch_sens_t<k>(P, smem, st, obs);                                                     \
     }
 #define ALIP_LAUNCH_DECL(k)                                                                            \
     hipError_t launch_lip_##k(bool solve, bool f32, const KP& P, size_t smem, hipStream_t st,          \
                               unsigned* res_out = nullptr);                                            \
     hipError_t launch_dd_##k(bool solve, const KP& P, size_t smem, hipStream_t st);                    \
-    hipError_t launch_sens_##k(const KP& P, size_t smem, hipStream_t st);
+    hipError_t launch_sens_##k(const KP& P, size_t smem, hipStream_t st, bool obs = false);
 ALIP_LAUNCH_DECL(1) ALIP_LAUNCH_DECL(2) ALIP_LAUNCH_DECL(3) ALIP_LAUNCH_DECL(4) ALIP_LAUNCH_DECL(5) ALIP_LAUNCH_DECL(6)
 #if ALIP_PART_N(1)
 ALIP_LAUNCHERS(1)

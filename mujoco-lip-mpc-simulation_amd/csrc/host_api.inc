@@ -1091,41 +1091,41 @@ int alipmpc_solve_batch(void* handle, int64_t B, const double* x0, const double*
 }
 
 // the sensitivity build's launch of a handle in its domain (fp64 wave program, N <= 5); P carries dfoot, du and sens_ok
-// in grad_out, J_out and active_out
-static hipError_t launch_sens(Handle* h, const KP& P, hipStream_t st)
+// in grad_out, J_out and active_out; obs: the obstacle-sensitivity build, with dfoot_obs and du_obs in c_out and cl_out
+static hipError_t launch_sens(Handle* h, const KP& P, hipStream_t st, bool obs = false)
 {
     const size_t smem = smem_bytes(h, true);
     switch (h->N) {
-    case 1: return launch_sens_1(P, smem, st);
-    case 2: return launch_sens_2(P, smem, st);
-    case 3: return launch_sens_3(P, smem, st);
-    case 4: return launch_sens_4(P, smem, st);
-    case 5: return launch_sens_5(P, smem, st);
+    case 1: return launch_sens_1(P, smem, st, obs);
+    case 2: return launch_sens_2(P, smem, st, obs);
+    case 3: return launch_sens_3(P, smem, st, obs);
+    case 4: return launch_sens_4(P, smem, st, obs);
+    case 5: return launch_sens_5(P, smem, st, obs);
     }
     return hipErrorInvalidValue;
 }
 
-// The solve with its sensitivities (DESIGN.md §3.7): one launch of the sensitivity build's work queue.  Its three
-// outputs reach the kernel in KP's eval-output slots (sens_wave.inc: sens_dfoot, sens_du, sens_okp), which a solve
-// launch leaves unused.
-int alipmpc_solve_sens_batch(void* handle, int64_t B, const double* x0, const double* goal, const int8_t* leg,
-                             const double* cir, const int32_t* nc, const double* elp, const int32_t* ne, const double* u0,
-                             const double* last_u, double* u_out, double* foot_out, double* x_pred, int32_t* status,
-                             int32_t* iters, double* dfoot, double* du, int32_t* sens_ok, void* hip_stream)
+// the calls of alipmpc_solve_sens_batch and alipmpc_solve_sens_obs_batch (obs)
+static int run_sens(Handle* h, bool obs, int64_t B, const double* x0, const double* goal, const int8_t* leg,
+                    const double* cir, const int32_t* nc, const double* elp, const int32_t* ne, const double* u0,
+                    double* u_out, double* foot_out, double* x_pred, int32_t* status, int32_t* iters, double* dfoot,
+                    double* du, int32_t* sens_ok, double* dfoot_obs, double* du_obs, void* hip_stream)
 {
-    Handle* h = (Handle*)handle;
-    (void)last_u;   // (DD only, and DD has no sensitivity build)
     if (!h) return ALIPMPC_EINVAL;
     const alipmpc_cfg& cf = h->cfg;
     if (cf.variant == ALIPMPC_VARIANT_DD) return fail(h, ALIPMPC_EUNSUPPORTED, "solve_sens: LIP variants only");
     if (cf.precision == ALIPMPC_PREC_FP32) return fail(h, ALIPMPC_EUNSUPPORTED, "solve_sens: fp64 handles only");
     if (h->lane_nct >= 0) return fail(h, ALIPMPC_EUNSUPPORTED, "solve_sens: wave-program handles only");
     if (h->N > 5) return fail(h, ALIPMPC_EUNSUPPORTED, "solve_sens: N <= 5 (the Gauss-Jordan solve's domain, n <= 15)");
+    const size_t PC = (size_t)alipmpc_sens_obs_cols(&cf);
+    if (obs && PC == 0) return fail(h, ALIPMPC_EINVAL, "solve_sens_obs: the handle has no obstacle slots");
+    if (obs && !dfoot_obs) return fail(h, ALIPMPC_EINVAL, "solve_sens_obs: dfoot_obs is required");
     if (B < 0) return fail(h, ALIPMPC_EINVAL, "B < 0");
     if (B == 0) return ALIPMPC_OK;
     const SceneIn scene{x0, goal, leg, cir, nc, elp, ne, u0};
     if (!scene_inputs_ok(cf, scene, true)) return fail(h, ALIPMPC_EINVAL, "missing input pointer");
-    if (!u_out || !dfoot) return fail(h, ALIPMPC_EINVAL, "u_out and dfoot are required");
+    if (!u_out || (!obs && !dfoot))
+        return fail(h, ALIPMPC_EINVAL, obs ? "u_out is required" : "u_out and dfoot are required");
     if (B >= (int64_t)1 << 31) return fail(h, ALIPMPC_EINVAL, "B >= 2^31 (32-bit work-queue counter)");
     HIPCHK(h, hipSetDevice(h->device));
     const int N = h->N;
@@ -1138,20 +1138,55 @@ int alipmpc_solve_sens_batch(void* handle, int64_t B, const double* x0, const do
     S.out(P.x_pred, x_pred, Bz * 5 * N);
     S.out(P.status, status, Bz);
     S.out(P.iters, iters, Bz);
-    double *d_dfoot = nullptr, *d_du = nullptr;
+    double *d_dfoot = nullptr, *d_du = nullptr, *d_dfo = nullptr, *d_duo = nullptr;
     int32_t* d_ok = nullptr;
     S.out(d_dfoot, dfoot, Bz * 3 * 7);
     S.out(d_du, du, Bz * 5 * N * 7);
     S.out(d_ok, sens_ok, Bz);
+    if (obs) {
+        S.out(d_dfo, dfoot_obs, Bz * 3 * PC);
+        S.out(d_duo, du_obs, Bz * 5 * N * PC);
+    }
     if (int e = S.commit()) return e;
     P.grad_out = d_dfoot;
     P.J_out = d_du;
     P.active_out = reinterpret_cast<int8_t*>(d_ok);
+    P.c_out = d_dfo;
+    P.cl_out = d_duo;
     TimedSpan span{h, S.st};
     if (int e = span.begin()) return e;
-    HIPCHK(h, launch_sens(h, P, S.st));
+    HIPCHK(h, launch_sens(h, P, S.st, obs));
     if (int e = span.end()) return e;
     return S.finish();
+}
+
+// The solve with its sensitivities (DESIGN.md §3.7): one launch of the sensitivity build's work queue.  Its three
+// outputs reach the kernel in KP's eval-output slots (sens_wave.inc: sens_dfoot, sens_du, sens_okp), which a solve
+// launch leaves unused.
+int alipmpc_solve_sens_batch(void* handle, int64_t B, const double* x0, const double* goal, const int8_t* leg,
+                             const double* cir, const int32_t* nc, const double* elp, const int32_t* ne, const double* u0,
+                             const double* last_u, double* u_out, double* foot_out, double* x_pred, int32_t* status,
+                             int32_t* iters, double* dfoot, double* du, int32_t* sens_ok, void* hip_stream)
+{
+    (void)last_u;   // (DD only, and DD has no sensitivity build)
+    return run_sens((Handle*)handle, false, B, x0, goal, leg, cir, nc, elp, ne, u0, u_out, foot_out, x_pred, status,
+                    iters, dfoot, du, sens_ok, nullptr, nullptr, hip_stream);
+}
+
+int32_t alipmpc_sens_obs_cols(const alipmpc_cfg* cfg) { return cfg ? 3 * cfg->nc_max + 5 * cfg->ne_max : 0; }
+
+// The solve with its sensitivities and their obstacle columns (DESIGN.md §3.10): one launch of the
+// obstacle-sensitivity build's work queue.  dfoot_obs and du_obs reach the kernel in two further eval-output slots (sens_wave.inc:
+// sens_dfoot_obs, sens_du_obs).
+int alipmpc_solve_sens_obs_batch(void* handle, int64_t B, const double* x0, const double* goal, const int8_t* leg,
+                                 const double* cir, const int32_t* nc, const double* elp, const int32_t* ne,
+                                 const double* u0, const double* last_u, double* u_out, double* foot_out,
+                                 double* x_pred, int32_t* status, int32_t* iters, double* dfoot, double* du,
+                                 int32_t* sens_ok, double* dfoot_obs, double* du_obs, void* hip_stream)
+{
+    (void)last_u;
+    return run_sens((Handle*)handle, true, B, x0, goal, leg, cir, nc, elp, ne, u0, u_out, foot_out, x_pred, status,
+                    iters, dfoot, du, sens_ok, dfoot_obs, du_obs, hip_stream);
 }
 
 int alipmpc_eval_batch(void* handle, int64_t B, const double* x0, const double* goal, const int8_t* leg,

@@ -1,6 +1,7 @@
 // Plan sensitivities of the wave program's fp64 solve (alipmpc_solve_sens_batch; DESIGN.md §3.7).  Device code,
-// included by alipmpc.hip after resto_wave.inc; only the sensitivity build of solve_one (SN = true, sens_kernel) calls
-// it, so no other instantiation holds a line of it.
+// included by alipmpc.hip after resto_wave.inc; only the sensitivity builds of solve_one (SN = 1, sens_kernel; SN = 2,
+// sens_obs_kernel, which adds the obstacle columns of alipmpc_solve_sens_obs_batch, DESIGN.md §3.10) call it, so no
+// other instantiation holds a line of it.
 //
 // At the accepted iterate of an instance that ended with status 0 or 1 the barrier KKT conditions of the slack
 // formulation, differentiated with mu and the prologue's decisions (obstacle selection, leg parity, the detour and its
@@ -147,20 +148,170 @@ __device__ __forceinline__ dd2 dd_gsum(dd2 v)
     return dd_add(dd2{ah, al}, dd2{bh, bl});
 }
 
+// ---- the obstacle columns (alipmpc_solve_sens_obs_batch, sens_obs_kernel; DESIGN.md §3.10)
+// The same system with further right-hand sides.  A parameter theta of the obstacle in selected slot j enters only the
+// N D-CBF rows (k, j), c = h(x_{k+1}) + (gamma - 1) h(x_k) with h = qa dx^2 + qb dx dy + qc dy^2 - ek on
+// (dx, dy) = pos - (ox, oy), so its column of the right-hand side is
+//     G^T sum_k [ -y_r d2c_r/dV dtheta + (dc_r/dV) Sigma_r (dc_r/dtheta) ] ,   r = row (k, j),
+// the first term from the y and the form entries hess_blocks puts into S for these rows (so K T + R t = 0 for a common
+// translation, up to rounding), the second as the state columns above: b_r = sqrt(Sigma_r) j_r times sqrt(Sigma_r)
+// dc_r/dtheta, exact products, double-double sums and elimination.  The centre enters through dx, dy of both states; a
+// shape parameter through (qa', qb', qc', ek'), its derivatives of the form: a circle's r has (0, 0, 0, 2 r), an
+// ellipse's a, b, phi follow from qa = (b cos)^2 + (a sin)^2, qb = 2 cos sin (b^2 - a^2), qc = (b sin)^2 + (a cos)^2,
+// ek = (a b)^2.  No E term: x0 does not move.
+// Columns are indexed by the caller's input slot (circle j: 3 j + cx, cy, r; ellipse j: 3 nc_max + 5 j + cx, cy, a, b,
+// phi); the prologue's keep masks (w.cst[K_SMAP]) give the selected slot.  A slot select_obs dropped, or one at or
+// above the instance's count, gets exact zeros.  One elimination per selected slot (5 right-hand sides, a circle uses 3), K
+// rebuilt from the kept double-double row parts and w.K, so the pivots are the first elimination's.
+constexpr int SENS_OBS_NR = 5;
+__device__ __forceinline__ double* sens_dfoot_obs(const KP& P) { return P.c_out; }   // B x 3 x PC
+__device__ __forceinline__ double* sens_du_obs(const KP& P) { return P.cl_out; }     // B x 5N x PC (nullable)
+
+// every obstacle column of instance b = v
 template <int N>
+__device__ __forceinline__ void sens_obs_fill(const KP& P, long long b, int lane, double v)
+{
+    const int PC = 3 * rfl(P.nc_max) + 5 * rfl(P.ne_max);
+    for (int i = lane; i < 3 * PC; i += WAVE) sens_dfoot_obs(P)[(size_t)b * 3 * PC + i] = v;
+    if (sens_du_obs(P))
+        for (int i = lane; i < 5 * N * PC; i += WAVE) sens_du_obs(P)[(size_t)b * 5 * N * PC + i] = v;
+}
+
+template <int N>
+__device__ __forceinline__ void sens_obs_columns(const KP& P, const WSS<N, double>& w, const double* G, long long b,
+                                                 int lane, const double (&kh)[Dim<N>::n], const double (&kl)[Dim<N>::n],
+                                                 int rps)
+{
+    using R = double;
+    using D = Dim<N>;
+    constexpr int n = D::n, NCP = D::NCP, KLD = D::KLD, NR = SENS_OBS_NR;
+    const int nc_max = rfl(P.nc_max), ne_max = rfl(P.ne_max), PC = 3 * nc_max + 5 * ne_max;
+    const long long kmb = __double_as_longlong(w.cst[K_SMAP]);
+    const uint32_t mc = (uint32_t)rfl((int)(kmb & 0xffffffffll)), me = (uint32_t)rfl((int)(kmb >> 32));
+    const int col = lane & 15;
+    const R gm1 = w.cst[K_GM1];
+    R* const dfo = sens_dfoot_obs(P) + (size_t)b * 3 * PC;
+    R* const duo = sens_du_obs(P) ? sens_du_obs(P) + (size_t)b * 5 * N * PC : nullptr;
+    for (int s = 0; s < nc_max + ne_max; ++s) {   // the caller's input slots: circles, then ellipses
+        const bool elp = s >= nc_max;
+        const int si = elp ? s - nc_max : s;
+        const uint32_t m = elp ? me : mc;
+        const int cb = elp ? 3 * nc_max + 5 * si : 3 * si, ncol = elp ? 5 : 3;
+        if (!((m >> si) & 1u)) {   // (wave-uniform) not selected: zero columns
+            for (int i = lane; i < 3 * ncol; i += WAVE) dfo[(i / ncol) * PC + cb + i % ncol] = R(0.0);
+            if (duo)
+                for (int i = lane; i < 5 * N * ncol; i += WAVE) duo[(size_t)(i / ncol) * PC + cb + i % ncol] = R(0.0);
+            continue;
+        }
+        const int pos = __builtin_popcount(m & ((1u << si) - 1u));
+        const int j6 = elp ? nc_max + pos : pos;   // the slot's row of obs6 and its place among a step's obstacle rows
+        // (qa', qb', qc', ek') of the shape parameters (columns 2 ..)
+        R dq[3][4];
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dq[p][i] = R(0.0);
+        if (!elp) {
+            dq[0][3] = 2 * w.obs[3 * pos + 2];
+        } else {
+            const R* e = w.obs + 3 * nc_max + 5 * pos;
+            const R ea = e[2], eb = e[3];
+            R sn, cs;
+            sincos(e[4], &sn, &cs);
+            const R qb = w.obs6[6 * j6 + 3];
+            dq[0][0] = 2 * ea * sn * sn; dq[0][1] = -4 * ea * cs * sn;
+            dq[0][2] = 2 * ea * cs * cs; dq[0][3] = 2 * ea * eb * eb;
+            dq[1][0] = 2 * eb * cs * cs; dq[1][1] = 4 * eb * cs * sn;
+            dq[1][2] = 2 * eb * sn * sn; dq[1][3] = 2 * ea * ea * eb;
+            dq[2][0] = -qb; dq[2][1] = 2 * (cs * cs - sn * sn) * (eb * eb - ea * ea); dq[2][2] = qb;
+        }
+        const R ox = w.obs6[6 * j6], oy = w.obs6[6 * j6 + 1];
+        const R qa = w.obs6[6 * j6 + 2], qb = w.obs6[6 * j6 + 3], qc = w.obs6[6 * j6 + 4];
+        R f1[NR], rh[NR], rl[NR];   // the y term (fp64: of order y q) and the Sigma term (double-double) of row `col`
+#pragma unroll
+        for (int c = 0; c < NR; ++c) f1[c] = rh[c] = rl[c] = R(0.0);
+        for (int k = 0; k < N; ++k) {
+            const int r = k * rps + 2 + j6;
+            const uint32_t pk = w.rgen[r];
+            R c0, c1, c2, c3;
+            ld4(w.rcoef + 4 * r, c0, c1, c2, c3);
+            const int t0 = gen_i(pk, 0), t1 = gen_i(pk, 1), t2 = gen_i(pk, 2), t3 = gen_i(pk, 3);
+            const R g0 = G[t0 * NCP + col], g1 = G[t1 * NCP + col], g2 = G[t2 * NCP + col], g3 = G[t3 * NCP + col];
+            const R sq = sqrt(w.rsig[r]), y = w.ry[r];
+            const R bj = sq * (c0 * g0 + c1 * g1 + c2 * g2 + c3 * g3);
+            const R x1 = w.V[t0] - ox, y1 = w.V[t1] - oy, x0 = w.V[t2] - ox, y0 = w.V[t3] - oy;
+            R ct[NR];
+            ct[0] = -(c0 + c2);
+            ct[1] = -(c1 + c3);
+            f1[0] += y * (2 * qa * g0 + qb * g1 + gm1 * (2 * qa * g2 + qb * g3));
+            f1[1] += y * (qb * g0 + 2 * qc * g1 + gm1 * (qb * g2 + 2 * qc * g3));
+#pragma unroll
+            for (int p = 0; p < 3; ++p) {
+                const R A = dq[p][0], Bq = dq[p][1], Cq = dq[p][2], Ek = dq[p][3];
+                ct[2 + p] = (A * x1 * x1 + Bq * x1 * y1 + Cq * y1 * y1 - Ek) +
+                            gm1 * (A * x0 * x0 + Bq * x0 * y0 + Cq * y0 * y0 - Ek);
+                f1[2 + p] -= y * ((2 * A * x1 + Bq * y1) * g0 + (2 * Cq * y1 + Bq * x1) * g1 +
+                                  gm1 * ((2 * A * x0 + Bq * y0) * g2 + (2 * Cq * y0 + Bq * x0) * g3));
+            }
+#pragma unroll
+            for (int c = 0; c < NR; ++c) {
+                const dd2 t = dd_add(dd2{rh[c], rl[c]}, dd_prod(bj, sq * ct[c]));
+                rh[c] = t.h;
+                rl[c] = t.l;
+            }
+        }
+        R a[n + NR], al[n + NR];
+#pragma unroll
+        for (int j = 0; j < n; ++j) {
+            const dd2 t = dd_add(dd2{kh[j], kl[j]}, dd2{w.K[col * KLD + j], R(0.0)});
+            a[j] = t.h;
+            al[j] = t.l;
+        }
+#pragma unroll
+        for (int c = 0; c < NR; ++c) {
+            const dd2 t = dd_add(dd2{rh[c], rl[c]}, dd2{f1[c], R(0.0)});
+            a[n + c] = t.h;
+            al[n + c] = t.l;
+        }
+        const bool ok = gj_regs_m<n, NR>(a, al, lane);   // (the first elimination's pivots: it cannot fail here)
+        const R qn = __longlong_as_double(0x7ff8000000000000ll);
+        wave_sync();   // (the last pass' reads of dp precede these writes)
+        if (lane < n) {
+#pragma unroll
+            for (int c = 0; c < NR; ++c) w.S[lane * 8 + c] = ok ? -a[n + c] : qn;
+        }
+        wave_sync();
+        for (int i = lane; i < 3 * ncol; i += WAVE)
+            dfo[(i / ncol) * PC + cb + i % ncol] = w.S[(i / ncol) * 8 + i % ncol];
+        if (duo) {
+            for (int i = lane; i < 5 * N * ncol; i += WAVE) {
+                const int l = i / ncol, c = i % ncol;
+                const int t = gx(l / 5 + 1, l % 5);
+                R v = R(0.0);
+                for (int j = 0; j < n; ++j) v = fma(G[t * NCP + j], w.S[j * 8 + c], v);
+                duo[(size_t)l * PC + cb + c] = v;
+            }
+        }
+    }
+    wave_sync();
+}
+
+// OB (the obstacle-sensitivity build, sens_obs_kernel): dfoot may be absent, and the obstacle columns get NaN as well
+template <int N, bool OB = false>
 __device__ __forceinline__ void sens_invalid(const KP& P, long long b, int lane)
 {
     const double qn = __longlong_as_double(0x7ff8000000000000ll);
-    if (lane < 3 * SENS_COLS) sens_dfoot(P)[(size_t)b * 3 * SENS_COLS + lane] = qn;
+    if (lane < 3 * SENS_COLS && (!OB || sens_dfoot(P))) sens_dfoot(P)[(size_t)b * 3 * SENS_COLS + lane] = qn;
     if (sens_du(P))
         for (int i = lane; i < 5 * N * SENS_COLS; i += WAVE) sens_du(P)[(size_t)b * 5 * N * SENS_COLS + i] = qn;
     if (sens_okp(P) && lane == 0) sens_okp(P)[b] = 0;
+    if constexpr (OB) sens_obs_fill<N>(P, b, lane, qn);
 }
 
 // the row state is solve_one's at its end: generator values rv, transcendentals ra0 / ra1, bound multipliers zl / zu and
 // inverse slack distances idl / idu of the accepted iterate; w.V holds the iterate, w.cst the (scaled) weights and the
 // effective goal
-template <int N, int KSM, int RPL>
+template <int N, int KSM, int RPL, bool OB = false>
 __device__ __forceinline__ void sens_epilogue(const KP& P, const WSS<N, double>& w, const double* G, long long b, int lane,
                                               bool valid, const int (&rtype)[RPL], const int (&rk)[RPL],
                                               const int (&roi)[RPL], const double (&rv)[RPL][4], const double (&ra0)[RPL],
@@ -174,7 +325,7 @@ __device__ __forceinline__ void sens_epilogue(const KP& P, const WSS<N, double>&
     static_assert(D::NT == 1 && n <= ALIP_GJ_MAX_N && n <= 16, "the gj_regs domain: n <= 15");
     static_assert(16 * 8 <= 64 * (N + 1), "R and dp (16 x 8) fit the Hessian-block buffer");
     if (!valid) {
-        sens_invalid<N>(P, b, lane);
+        sens_invalid<N, OB>(P, b, lane);
         return;
     }
     const int g4 = lane >> 4, col = lane & 15;
@@ -320,7 +471,7 @@ __device__ __forceinline__ void sens_epilogue(const KP& P, const WSS<N, double>&
     }
     wave_sync();
     if (!gj_regs_m<n, NR>(a, al, lane)) {   // a pivot <= 0 at delta = 0: no regularisation, the sensitivity is invalid
-        sens_invalid<N>(P, b, lane);
+        sens_invalid<N, OB>(P, b, lane);
         return;
     }
     // ---- dp / dtheta = -K^-1 R; dfoot = its rows of p_0; du = E + G dp on the rows of x_1 .. x_N
@@ -328,7 +479,7 @@ __device__ __forceinline__ void sens_epilogue(const KP& P, const WSS<N, double>&
 #pragma unroll
         for (int c = 0; c < NR; ++c) w.S[lane * 8 + c] = -a[n + c];
     }
-    if (lane < 3) {
+    if (lane < 3 && (!OB || sens_dfoot(P))) {
 #pragma unroll
         for (int c = 0; c < NR; ++c) sens_dfoot(P)[((size_t)b * 3 + lane) * NR + c] = -a[n + c];
     }
@@ -350,4 +501,5 @@ __device__ __forceinline__ void sens_epilogue(const KP& P, const WSS<N, double>&
     }
     if (sens_okp(P) && lane == 0) sens_okp(P)[b] = 1;
     wave_sync();
+    if constexpr (OB) sens_obs_columns<N>(P, w, G, b, lane, kh, kl, rps);
 }

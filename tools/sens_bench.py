@@ -1,13 +1,16 @@
-"""Cost of the plan sensitivities: solve_sens against solve on the same handle and batch.
+"""Cost of the plan sensitivities: solve_sens and solve_sens_obs against solve on the same handle and batch (DESIGN.md
+§3.7, §3.10).
 
-Scenes are generated on the device; every repetition runs three legs in turn on device pointers and reads
+Scenes are generated on the device; every repetition runs four legs in turn on device pointers and reads
 alipmpc_last_kernel_ms after each:
   solve       alipmpc_solve_batch as the batch API launches it (a split launch where B fits the resident slots)
   solve_1ph   the one-phase launch of the same handle: the same call on a second handle created with the split off
               (ALIPMPC_SPLIT_IT=0 while it is created), i.e. what solve_sens adds its epilogue to
   solve_sens  alipmpc_solve_sens_batch
-The line reports the medians, solve_sens over solve_1ph, what the split launch is worth (solve_1ph over solve), the
-valid share, and checks that the three legs return the same plan.
+  solve_sens_obs  alipmpc_solve_sens_obs_batch (every output, the obstacle columns included)
+The line reports the medians, solve_sens and solve_sens_obs over solve_1ph, solve_sens_obs over solve_sens and over the
+2 P one-phase solves that finite differences of the obstacle columns would cost, what the split launch is worth
+(solve_1ph over solve), the valid share, and checks that the legs return the same plan and the same state columns.
 
   timeout 600 python tools/sens_bench.py --B 4096                               # cfg2's shape
   timeout 900 python tools/sens_bench.py --B 65536 --N 5 --n-cir 5 --n-elp 5    # cfg3's shape
@@ -57,17 +60,22 @@ def main():
         inp.update(elp=torch.empty((B, ne, 5), **f64), ne=torch.empty(B, **i32))
     s.scenes_device(inp, seed=a.seed, n_cir=nc, n_elp=ne)
 
-    def outs(sens):
+    P = s.sens_obs_cols
+
+    def outs(sens, obs=False):
         o = dict(u=torch.empty((B, s.n), **f64), foot=torch.empty((B, 3), **f64), x_pred=torch.empty((B, N, 5), **f64),
                  status=torch.empty(B, **i32), iters=torch.empty(B, **i32))
         if sens:
             o.update(dfoot=torch.empty((B, 3, 7), **f64), du=torch.empty((B, s.n, 7), **f64), sens_ok=torch.empty(B, **i32))
+        if obs:
+            o.update(dfoot_obs=torch.empty((B, 3, P), **f64), du_obs=torch.empty((B, s.n, P), **f64))
         return o
 
-    o_s, o_1, o_x = outs(False), outs(False), outs(True)
+    o_s, o_1, o_x, o_o = outs(False), outs(False), outs(True), outs(True, True)
     legs = dict(solve=lambda: s.solve_device(inp, o_s), solve_1ph=lambda: s1.solve_device(inp, o_1),
-                solve_sens=lambda: s.solve_sens_device(inp, o_x))
-    who = dict(solve=s, solve_1ph=s1, solve_sens=s)
+                solve_sens=lambda: s.solve_sens_device(inp, o_x),
+                solve_sens_obs=lambda: s.solve_sens_obs_device(inp, o_o))
+    who = dict(solve=s, solve_1ph=s1, solve_sens=s, solve_sens_obs=s)
     for f in legs.values():   # warm-up: code objects, record buffers
         f()
     torch.cuda.synchronize()
@@ -78,7 +86,10 @@ def main():
             torch.cuda.synchronize()
             ms[k].append(who[k].last_kernel_ms())
     for k in ("u", "foot", "x_pred", "status", "iters"):
-        assert torch.equal(o_s[k], o_x[k]) and torch.equal(o_1[k], o_x[k]), k
+        assert torch.equal(o_s[k], o_x[k]) and torch.equal(o_1[k], o_x[k]) and torch.equal(o_o[k], o_x[k]), k
+    for k in ("dfoot", "du"):
+        assert torch.equal(torch.nan_to_num(o_o[k], nan=7.0), torch.nan_to_num(o_x[k], nan=7.0)), k
+    assert torch.equal(o_o["sens_ok"], o_x["sens_ok"])
     it = o_x["iters"].double()
     med = {k: statistics.median(v) for k, v in ms.items()}
     rec = {"tool": "sens_bench", "build_id": alipmpc.build_id(), "B": B, "N": N, "n_cir": nc, "n_elp": ne,
@@ -88,6 +99,10 @@ def main():
            "ms_min": {k: round(min(v), 4) for k, v in ms.items()},
            "ms_all": {k: [round(x, 4) for x in v] for k, v in ms.items()},
            "sens_over_solve_1ph": round(med["solve_sens"] / med["solve_1ph"], 4),
+           "obs_cols": P,
+           "sens_obs_over_solve_1ph": round(med["solve_sens_obs"] / med["solve_1ph"], 4),
+           "sens_obs_over_sens": round(med["solve_sens_obs"] / med["solve_sens"], 4),
+           "sens_obs_over_2P_solves_1ph": round(med["solve_sens_obs"] / (2 * P * med["solve_1ph"]), 4),
            "solve_1ph_over_solve": round(med["solve_1ph"] / med["solve"], 4),
            "iters_mean": round(float(it.mean().item()), 2), "iters_max": int(it.max().item()),
            "sens_ok_share": round(float((o_x["sens_ok"] == 1).double().mean().item()), 4),
