@@ -21,14 +21,20 @@
  *   - The caller owns every buffer.  hip_stream == NULL: all pointers are HOST pointers; the library
  *     stages them through its own device workspace and synchronises before returning.
  *     hip_stream != NULL: all pointers are DEVICE pointers (hipMalloc / torch CUDA tensors) and the call
- *     is asynchronous on that stream (no host synchronisation; graph-capturable).  The only device allocation
- *     is the split launch's record buffer (alipmpc_solve_launches): one per stream, made by the stream's first
- *     split solve, sized for the resident slots (per slot one loop-state record and three index words: the record's
+ *     is asynchronous on that stream (no host synchronisation; graph-capturable).  The device allocations are two
+ *     per-stream buffers, the split launch's record buffer and the hand-off list (below), both made outside a capture
+ *     only and kept until alipmpc_destroy.  The record buffer (alipmpc_solve_launches): one per stream, made by the
+ *     stream's first split solve, sized for the resident slots (per slot one loop-state record and three index words: the record's
  *     instance and the two class lists of the paired phase 2) and kept until alipmpc_destroy — a capture on a stream that has
  *     none yet records the one-phase form.  A captured graph uses its capture stream's buffer: replay it on that
  *     stream (or ordered with the solves there).  At most 8 streams per handle hold one (kept until destroy, never
- *     evicted); solves on a further stream run the one-phase form (same bits).  ALIPMPC_STREAM_NULL selects device pointers on
- *     the null (default) stream, whose handle value is 0.
+ *     evicted); solves on a further stream run the one-phase form (same bits).  The hand-off list (lane program, and fp32
+ *     wave program with cfg.restoration = ALIPMPC_RESTORATION_IPOPT: alipmpc_lane_handoffs): one per stream, B + 1 words,
+ *     allocated by the stream's first uncaptured lane or fp32 solve.  It grows only outside a capture — a larger batch
+ *     gets a new list of at least twice the bytes, without synchronising — and the old lists are kept until
+ *     alipmpc_destroy, so queued launches and captured graphs that hold one stay valid.  A capture therefore needs an
+ *     earlier uncaptured solve of at least its B on that stream; without one the captured call fails with ALIPMPC_EHIP.
+ *     ALIPMPC_STREAM_NULL selects device pointers on the null (default) stream, whose handle value is 0.
  *   - Every LIP solve launch takes one of the handle's 64 work-queue counter pairs (a ring; each pair is
  *     reset by the last wave of the launch that used it).  A solve captured into a hipGraph bakes in one
  *     pair: do not replay such a graph concurrently with itself, and keep fewer than 64 solve launches of
@@ -599,7 +605,9 @@ int alipmpc_solve_launches(void* handle, int64_t B, int32_t* launches, int32_t* 
 /* Lane program (either precision) or fp32 wave program with cfg.restoration = ALIPMPC_RESTORATION_IPOPT: the instances
  * of the last solve on this stream whose line search failed in that program and which were therefore solved, from
  * their start, by the fp64 wave program's restoration-capable work queue (IPOPT's restoration phase: DESIGN.md §2
- * item 4).  Synchronises the stream.  0 for other programs / restoration modes.  No reference counterpart. */
+ * item 4).  Synchronises the stream.  0 for other programs / restoration modes.  The count is read from the stream's
+ * current list: a graph captured before the list grew (Conventions) counts into the list it captured, so after its
+ * replay this call still reports the last solve issued through the library.  No reference counterpart. */
 int alipmpc_lane_handoffs(void* handle, void* hip_stream, int64_t* count);
 
 /* The device program this handle's solves run (cfg.program): "solve_kernel<N,rows/4,type>" (one instance per

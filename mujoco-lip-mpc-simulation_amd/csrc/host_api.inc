@@ -57,9 +57,16 @@ struct Handle {
     };
     std::map<hipStream_t, SplitBuf> split;
     std::mutex split_mtx;
-    // lane program with cfg.restoration = IPOPT: per stream, the list of instances handed to the wave program (count +
-    // indices; grown to the largest batch seen, never freed before alipmpc_destroy)
+    // lane program and fp32 wave program with cfg.restoration = IPOPT: per stream, the list of instances handed to the
+    // fp64 wave program (count + indices).  A list too small for a batch is RETIRED, not freed: the stream gets a new
+    // one of at least twice the bytes and the old one is kept here until alipmpc_destroy, so a graph captured on the
+    // stream keeps a valid pointer whatever batch sizes run on that stream later (redo_list)
     std::map<hipStream_t, SplitBuf> redo;
+    struct Retired {
+        hipStream_t st;
+        SplitBuf buf;
+    };
+    std::vector<Retired> redo_retired;   // newest last
     // launch timing: a ring of event pairs, so a re-record never targets an event still pending on the
     // stream (that serialises the host with the previous launch)
     static constexpr int NEV = 16;
@@ -384,7 +391,10 @@ int ksm_of(int rows)
 }
 
 // cfg.restoration = IPOPT, fp32 programs and the lane program: the stream's hand-off list ([0] = count, then the
-// instances), allocated outside a capture (a capture needs an uncaptured solve of that size on the stream first)
+// instances), allocated outside a capture (a capture needs an uncaptured solve of at least its B on the stream first).
+// A list too small for B is retired to Handle::redo_retired, where it stays allocated until alipmpc_destroy: launches
+// already queued and graphs already captured go on using it, so growth neither frees nor synchronises.  The new list
+// holds max(need, twice the old bytes): the retired lists of a stream sum to less than its live one.
 static hipError_t redo_list(const Handle* h, hipStream_t st, long long B, uint32_t** out)
 {
     Handle* hm = const_cast<Handle*>(h);
@@ -394,14 +404,11 @@ static hipError_t redo_list(const Handle* h, hipStream_t st, long long B, uint32
     if (rb.bytes < need) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return hipErrorNotSupported;
-        if (rb.p) {
-            (void)hipStreamSynchronize(st);
-            (void)hipFree(rb.p);
-            rb.p = nullptr;
-            rb.bytes = 0;
-        }
-        if (hipError_t e = hipMalloc(&rb.p, need)) return e;
-        rb.bytes = need;
+        Handle::SplitBuf nb;
+        nb.bytes = std::max(need, 2 * rb.bytes);
+        if (hipError_t e = hipMalloc(&nb.p, nb.bytes)) return e;
+        if (rb.p) hm->redo_retired.push_back({st, rb});
+        rb = nb;
     }
     *out = (uint32_t*)rb.p;
     return hipSuccess;
@@ -2062,6 +2069,30 @@ int alipmpc_dbg_kkt_solves(int form, int n, int fp32, const double* sys, int nsy
     return ok_ ? 0 : -1;
 }
 
+// test hook (not part of the ABI): the hand-off lists the handle owns for a stream (hip_stream as the batch calls read
+// it) — the live one first, then the retired ones, newest first; fills up to cap (address, bytes) pairs and returns the
+// number of lists, or -1 on a bad argument.  Host bookkeeping only: no device memory is touched, nothing synchronises.
+int alipmpc_dbg_handoff_lists(void* handle, void* hip_stream, uint64_t* addr, uint64_t* bytes, int cap)
+{
+    Handle* h = (Handle*)handle;
+    if (!h || cap < 0 || (cap > 0 && (!addr || !bytes))) return -1;
+    const hipStream_t st = stream_of(h, hip_stream);
+    std::lock_guard<std::mutex> lk(h->split_mtx);
+    int n = 0;
+    auto put = [&](const Handle::SplitBuf& b) {
+        if (n < cap) {
+            addr[n] = (uint64_t)(uintptr_t)b.p;
+            bytes[n] = (uint64_t)b.bytes;
+        }
+        ++n;
+    };
+    auto it = h->redo.find(st);
+    if (it != h->redo.end() && it->second.p) put(it->second);
+    for (auto r = h->redo_retired.rbegin(); r != h->redo_retired.rend(); ++r)
+        if (r->st == st) put(r->buf);
+    return n;
+}
+
 const char* alipmpc_build_id(void)
 {
 #ifdef ALIP_BUILD_ID
@@ -2175,6 +2206,8 @@ void alipmpc_destroy(void* handle)
         if (kv.second.p) hipFree(kv.second.p);
     for (auto& kv : h->redo)
         if (kv.second.p) hipFree(kv.second.p);
+    for (auto& r : h->redo_retired)
+        if (r.buf.p) hipFree(r.buf.p);
     for (auto& pr : h->ev)
         for (hipEvent_t e : pr)
             if (e) hipEventDestroy(e);

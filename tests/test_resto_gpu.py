@@ -343,7 +343,8 @@ def test_handoff_equals_fp64_wave_program(gpu_lib, coracle, name):
     does not say), and at least 100 are handed off.  A second solve gives the same bits and the same count (the list
     starts empty at every solve), and so do solves through device pointers on a stream of the caller's.  On the
     oracle's R stratum, at the handle's tolerances, the status and foothold shares reach the same-tolerance oracle's
-    self shares minus MARGIN."""
+    self shares minus MARGIN.  (The list across graph capture and growth, and with many solves in flight:
+    tests/test_streams_gpu.py.)"""
     import torch
     row, kw, tols = HANDLES[name]
     variant, N, n_cir, n_elp, B, _ = ROWS[row]
