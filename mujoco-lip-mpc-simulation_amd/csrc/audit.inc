@@ -476,11 +476,11 @@ static hipError_t launch_audit(int N, const AuP& A, hipStream_t st)
 }
 
 // ------------------------------------------------------------------------------------------------
-// The guard of the scheduled closed loop's first-order ticks (cfg.cl_between = ALIPMPC_CL_BETWEEN_GUARDED, alipmpc.hip:
+// The guard of the scheduled closed loop's first-order ticks (cfg.cl_between = ALIPMPC_CL_BETWEEN_GUARDED, closed_loop.inc:
 // cl_between_run_kernel).  Before a first-order tick commands u_fo = ua + du[:, 0:5] (x_nex - xa), this kernel holds it
 // against the eval hook's rows at the tick's own x_nex — alipmpc_audit_batch's column 0 of (x0 = x_nex, u = u_fo,
 // leg = -leg_ind), obstacle selection at x_nex included — and sets CL_FLAG_FIRED where !(viol <= tol): that episode
-// re-solves on this tick instead (host_api.inc).  The audit's mapping: one episode per 16-lane row, 16 per workgroup,
+// re-solves on this tick instead (closed_loop_host.inc).  The audit's mapping: one episode per 16-lane row, 16 per workgroup,
 // grid-stride, the workspace of a group in LDS (AWS without the clearance pass's parts); episodes that have stopped or
 // have no anchor are skipped.  x_nex is formed by every lane of the row (cl_flow, the tick kernels' expression), u_fo by
 // the lane that owns the component (cl_first_order_plan's sum).  A plan or state that is not finite has viol = NaN, as

@@ -1274,484 +1274,7 @@ int alipmpc_rollout_batch(void* handle, int64_t B, int32_t S, const double* x0, 
     return Z.finish();
 }
 
-// the dataset end of alipmpc_closed_loop_dataset_batch (nullptr: alipmpc_closed_loop_batch)
-struct DsArgs {
-    int64_t first_index;
-    double safe_dis;
-    int64_t max_rows;
-    double *X, *y_mpc, *y_act;
-    int32_t* row_status;
-    int64_t* row_start;
-};
-
-// a schedule of alipmpc_closed_loop_schedule_batch (nullptr: every tick solves, whatever f_cyc is)
-struct SchedArgs {
-    uint64_t mask;       // bit i: tick i of every step solves
-    double* plan_traj;   // B x S x f_cyc x 5N or NULL
-};
-
-// the closed-loop entry points.  Without ds and sch the launches, grouping and results are those of
-// alipmpc_closed_loop_batch as it always was: everything the dataset and the schedule add is registered after the
-// existing areas and sits behind a test of ds / sch.
-static int closed_loop_impl(Handle* h, int64_t B, int32_t S, int32_t f_cyc, double kick, uint64_t seed,
-                            const double* x0, const double* foot0, const double* goal, const int8_t* leg,
-                            const double* cir, const int32_t* nc, const double* elp, const int32_t* ne,
-                            double* foot_traj, double* x_traj, double* hd_traj, int32_t* status_traj,
-                            int32_t* iters_traj, int32_t* steps_to_goal, double* action_traj, void* hip_stream,
-                            const DsArgs* ds, const SchedArgs* sch = nullptr)
-{
-    if (!h) return ALIPMPC_EINVAL;
-    const alipmpc_cfg& cf = h->cfg;
-    if (cf.variant == ALIPMPC_VARIANT_DD) return fail(h, ALIPMPC_EUNSUPPORTED, "closed loop: LIP variants only");
-    if (B < 0 || S < 0 || f_cyc < 1 || !(kick >= 0)) return fail(h, ALIPMPC_EINVAL, "B, S < 0, f_cyc < 1 or kick < 0");
-    if (sch) {
-        if (f_cyc > CL_MAX_F) return fail(h, ALIPMPC_EINVAL, "closed loop schedule: f_cyc outside 1..64");
-        if (f_cyc < 64 && (sch->mask >> f_cyc) != 0)
-            return fail(h, ALIPMPC_EINVAL, "closed loop schedule: mpc_mask has a tick at or above f_cyc");
-    }
-    const int ncx = 3 * cf.nc_max + 5 * cf.ne_max + 11;   // columns of X
-    if (ds) {
-        if (ds->first_index < 0 || ds->first_index > (int64_t)1 << 32 || ds->first_index + B > (int64_t)1 << 32)
-            return fail(h, ALIPMPC_EINVAL, "closed loop dataset: first_index < 0 or first_index + B > 2^32");
-        if (!(ds->safe_dis >= 0) || !std::isfinite(ds->safe_dis))
-            return fail(h, ALIPMPC_EINVAL, "closed loop dataset: safe_dis negative or not finite");
-        if (ds->max_rows < 0) return fail(h, ALIPMPC_EINVAL, "closed loop dataset: max_rows < 0");
-        if ((long long)S * f_cyc * ncx > 0x7fffffffLL)
-            return fail(h, ALIPMPC_EINVAL, "closed loop dataset: S * f_cyc * columns of X > 2^31 - 1");
-        if (B == 0 || S == 0) {   // no rows: row_start is all zero
-            if (ds->row_start) {
-                if (hip_stream == nullptr) {
-                    std::memset(ds->row_start, 0, ((size_t)B + 1) * 8);
-                } else {
-                    HIPCHK(h, hipSetDevice(h->device));
-                    HIPCHK(h, hipMemsetAsync(ds->row_start, 0, ((size_t)B + 1) * 8, stream_of(h, hip_stream)));
-                }
-            }
-            return ALIPMPC_OK;
-        }
-    }
-    if (B == 0 || S == 0) return ALIPMPC_OK;
-    if (!foot0 || !scene_inputs_ok(cf, SceneIn{x0, goal, leg, cir, nc, elp, ne, nullptr}, false))
-        return fail(h, ALIPMPC_EINVAL, "missing input pointer");
-    HIPCHK(h, hipSetDevice(h->device));
-    const int N = h->N, n = 5 * N;
-    const size_t Bz = (size_t)B, Sz = (size_t)S, Fz = (size_t)f_cyc;
-    // dataset: are rows wanted (or row_start alone), and the rows the host-mode copies of the row arrays hold
-    const bool ds_rows = ds && (ds->X || ds->y_mpc || ds->y_act || ds->row_status);
-    const size_t ds_cap = ds ? std::min<size_t>((size_t)ds->max_rows, Bz * Sz * Fz) : 0;
-    CLP C;
-    std::memset(&C, 0, sizeof(C));
-    KP P = make_kp(h, B, true);
-    DsP D;
-    std::memset(&D, 0, sizeof(D));
-    Staging Z(h, hip_stream, true);
-    const hipStream_t st = Z.st;
-    const bool host = Z.host;
-    // the working set: plant and controller state, each tick's solve inputs and outputs
-    Z.work(C.vdes, Bz * 2); Z.work(C.pose0, Bz * 3);
-    Z.work(C.x, Bz * 5); Z.work(C.pst, Bz * 2); Z.work(C.hdv, Bz * 4);
-    Z.work(C.mhd, Bz * 3); Z.work(C.plan, Bz * n); Z.work(C.xs, Bz * 5);
-    Z.work(C.u0, Bz * n); Z.work(P.u_out, Bz * n); Z.work(P.foot_out, Bz * 3);
-    Z.work(P.x_pred, Bz * n); Z.work(C.leg, Bz); Z.work(C.sleg, Bz);
-    Z.work(C.flags, Bz); Z.work(C.active, Bz); Z.work(P.status, Bz);
-    Z.work(P.iters, Bz);
-    int32_t* ord = nullptr;
-    Z.work(ord, Bz);
-    stage_scene(Z, P, h, SceneIn{nullptr, goal, nullptr, cir, nc, elp, ne, nullptr}, Bz);
-    Z.out(C.foot_traj, foot_traj, Bz * Sz * 3);
-    Z.out(C.x_traj, x_traj, Bz * (Sz + 1) * 5);
-    Z.out(C.hd_traj, hd_traj, Bz * Sz * 2);
-    // (row_status is compacted from the ticks' statuses: they are kept even when the caller does not ask for them)
-    if (status_traj || !(ds_rows && ds->row_status)) Z.out(C.status_traj, status_traj, Bz * Sz * Fz);
-    else Z.work(C.status_traj, Bz * Sz * Fz);
-    Z.out(C.iters_traj, iters_traj, Bz * Sz * Fz);
-    Z.out(C.steps_to_goal, steps_to_goal, Bz);
-    Z.out(C.action_traj, action_traj, Bz * Sz * Fz * 8);
-    double* d_plan = nullptr;
-    if (sch) Z.out(d_plan, sch->plan_traj, Bz * Sz * Fz * (size_t)n);
-    long long* d_rs = nullptr;
-    if (ds) {   // host mode reads row_start back itself (below): the rows are downloaded once their number is known
-        if (host || !ds->row_start) Z.work(d_rs, Bz + 1);
-        else d_rs = (long long*)ds->row_start;
-        Z.work(C.ds_nst, Bz);
-        if (ds_rows) {
-            Z.work(C.ds_step, Bz * Sz * DS_STEP);
-            Z.work(C.ds_tick, Bz * Sz * Fz * DS_TICK);
-            Z.out_area(D.X, ds->X, ds_cap * (size_t)ncx);
-            Z.out_area(D.y_mpc, ds->y_mpc, ds_cap * 8);
-            Z.out_area(D.y_act, ds->y_act, ds_cap * 8);
-            Z.out_area(D.row_status, ds->row_status, ds_cap);
-        }
-    }
-    // first-order ticks (cfg.cl_between, a scheduled loop only): each episode's anchor, and the other two outputs of
-    // the sensitivity build (a host-pointer schedule registers 32 slots, + 5: within Staging::MAX_SLOTS)
-    const bool guarded = sch && cf.cl_between == ALIPMPC_CL_BETWEEN_GUARDED;   // (mode 1 with the guard, below)
-    const bool fo_mode = (sch && cf.cl_between == ALIPMPC_CL_BETWEEN_FIRST_ORDER) || guarded;
-    struct {
-        double *xa, *ua, *du, *dfoot;
-        int32_t* ok;
-    } an{};
-    if (fo_mode) {
-        Z.work(an.xa, Bz * 5); Z.work(an.ua, Bz * n); Z.work(an.du, Bz * n * 7); Z.work(an.dfoot, Bz * 21);
-        Z.work(an.ok, Bz);
-    }
-    if (int e = Z.commit()) {
-        if (Z.alloc_err == hipSuccess) return e;
-        (void)hipGetLastError();
-        return fail(h, ALIPMPC_EHIP, "closed loop: workspace of " + std::to_string(Z.need) + " bytes" +
-                    (ds_rows ? " (row staging " + std::to_string(Bz * Sz * Fz * DS_TICK * 8) + " bytes)" : "") +
-                    ": " + hipGetErrorString(Z.alloc_err));
-    }
-    if (int e = Z.put(C.x, x0, Bz * 5 * 8)) return e;
-    if (int e = Z.put(C.pst, foot0, Bz * 2 * 8)) return e;
-    if (int e = Z.put(C.leg, leg, Bz)) return e;
-    C.B = B; C.S = S; C.f = f_cyc; C.variant = cf.variant; C.N = N; C.kick = kick; C.seed = (unsigned long long)seed;
-    C.goal = P.goal; C.u = P.u_out; C.foot = P.foot_out; C.x_pred = P.x_pred; C.status = P.status; C.iters = P.iters;
-    const AlipMats am = alip_mats(cf);
-    const double beta = am.beta, T = cf.dt, dt = T / f_cyc;
-    alip_des_vel(am, T, 0.6, C.vdx, C.vdy0);
-    C.ch_d = std::cosh(beta * dt); C.shb_d = std::sinh(beta * dt) / beta; C.bsh_d = std::sinh(beta * dt) * beta;
-    C.td = dt / T;
-    const unsigned g1 = (unsigned)((B + 255) / 256);
-    hipLaunchKernelGGL(cl_init_kernel, dim3(g1), dim3(256), 0, st, C);
-    HIPCHK(h, hipGetLastError());
-    P.x0 = C.xs; P.leg = C.sleg; P.u0 = C.u0; P.active = C.active;
-    // longest-first launch order of each tick (wave program; opt-in, ALIPMPC_CL_ORDER=1): it puts at most one long
-    // instance on a SIMD, but a tick's time is set by its single slowest instance, a warm-started one whose line
-    // search halves ~20 times per iteration (tools/cl_wstamps.py, profiles/r3/wst): 52.13 vs 52.00 ms per loop
-    const char* oe = std::getenv("ALIPMPC_CL_ORDER");
-    const bool order_ok = cf.program != ALIPMPC_PROGRAM_LANE && oe && std::strcmp(oe, "1") == 0;
-    // Episode groups (ALIPMPC_CL_GROUPS, >= 256 episodes each): contiguous ranges of episodes whose ticks run on
-    // streams of their own, so a tick that waits on one slow instance holds back only its group; the other groups'
-    // launches fill the device meanwhile.  Every episode runs the same kernels on the same values (the kick is seeded
-    // by the global episode index), so the outputs do not depend on the grouping (GPU test).
-    int G = env_groups();
-#ifdef ALIP_WSTAMP
-    G = 1;   // (diagnostic records are indexed by the whole batch)
-#endif
-    if (order_ok) G = 1;   // (the opt-in launch order is a permutation of the whole batch)
-    G = (int)std::max<long long>(1, std::min<long long>({(long long)G, (long long)Handle::MAXG, B / 256}));
-    struct Grp {
-        CLP C;
-        KP P;
-        hipStream_t s;
-        unsigned g1;
-        double* plan_traj;
-        double *xa, *ua, *du, *dfoot;   // first-order mode: the group's anchors and sensitivity outputs
-        int32_t* ok;
-    } grp[Handle::MAXG];
-    const long long nn = n, SF = (long long)S * f_cyc;
-    for (int g = 0; g < G; ++g) {
-        const long long b0 = B * g / G, Bg = B * (g + 1) / G - b0;
-        auto o = [&](auto& p, long long per) {
-            if (p) p += b0 * per;
-        };
-        CLP c = C;
-        c.B = Bg;
-        c.b0 = (ds ? (long long)ds->first_index : 0) + b0;
-        o(c.goal, 2); o(c.x, 5); o(c.pst, 2); o(c.hdv, 4); o(c.mhd, 3); o(c.plan, nn); o(c.leg, 1); o(c.flags, 1);
-        o(c.xs, 5); o(c.u0, nn); o(c.sleg, 1); o(c.u, nn); o(c.foot, 3); o(c.x_pred, nn); o(c.status, 1);
-        o(c.iters, 1); o(c.active, 1); o(c.foot_traj, 3LL * S); o(c.x_traj, 5LL * (S + 1)); o(c.hd_traj, 2LL * S);
-        o(c.status_traj, SF); o(c.iters_traj, SF); o(c.steps_to_goal, 1); o(c.action_traj, 8 * SF); o(c.vdes, 2);
-        o(c.pose0, 3);
-        o(c.ds_tick, DS_TICK * SF); o(c.ds_step, (long long)DS_STEP * S); o(c.ds_nst, 1);
-        KP q = P;
-        q.B = Bg;
-        o(q.goal, 2); o(q.cir, 3LL * cf.nc_max); o(q.nc, 1); o(q.elp, 5LL * cf.ne_max); o(q.ne, 1); o(q.x0, 5);
-        o(q.leg, 1); o(q.u0, nn); o(q.active, 1); o(q.u_out, nn); o(q.foot_out, 3); o(q.x_pred, nn); o(q.status, 1);
-        o(q.iters, 1);
-        grp[g].C = c;
-        grp[g].P = q;
-        grp[g].g1 = (unsigned)((Bg + 255) / 256);
-        grp[g].plan_traj = d_plan ? d_plan + b0 * SF * nn : nullptr;
-        grp[g].xa = an.xa; grp[g].ua = an.ua; grp[g].du = an.du; grp[g].dfoot = an.dfoot; grp[g].ok = an.ok;
-        o(grp[g].xa, 5); o(grp[g].ua, nn); o(grp[g].du, 7 * nn); o(grp[g].dfoot, 21); o(grp[g].ok, 1);
-        grp[g].s = st;
-        if (G > 1) {
-            if (!h->gst[g]) HIPCHK(h, hipStreamCreateWithFlags(&h->gst[g], hipStreamNonBlocking));
-            if (!h->gev[g]) HIPCHK(h, hipEventCreateWithFlags(&h->gev[g], hipEventDisableTiming));
-            grp[g].s = h->gst[g];
-        }
-    }
-    if (G > 1 && !h->gev[Handle::MAXG]) HIPCHK(h, hipEventCreateWithFlags(&h->gev[Handle::MAXG], hipEventDisableTiming));
-    TimedSpan span{h, st};
-    if (int e = span.begin()) return e;
-    if (G > 1) {   // fork
-        HIPCHK(h, hipEventRecord(h->gev[Handle::MAXG], st));
-        for (int g = 0; g < G; ++g) HIPCHK(h, hipStreamWaitEvent(grp[g].s, h->gev[Handle::MAXG], 0));
-    }
-    // a scheduled loop's nominal ticks: the arguments every run shares (the rest-flow constants of every tick index,
-    // by the expressions of the solve ticks below), and whether a maximal run is one launch (ALIPMPC_CL_FUSE=0: a
-    // launch per tick, for the A/B comparison)
-    CLN Qn;
-    bool fuse = true;
-    if (sch) {
-        std::memset(&Qn, 0, sizeof(Qn));
-        Qn.bsh = am.A[10]; Qn.ch = am.ch; Qn.ibv = 1.0 / am.B[6];
-        for (int i = 0; i < f_cyc; ++i) {
-            const double rest = T - i * (T / f_cyc);
-            Qn.rest[i][0] = std::cosh(beta * rest); Qn.rest[i][1] = std::sinh(beta * rest) / beta;
-            Qn.rest[i][2] = std::sinh(beta * rest) * beta; Qn.rest[i][3] = rest * (1.0 / T);
-        }
-        const char* fe = std::getenv("ALIPMPC_CL_FUSE");
-        fuse = !(fe && std::strcmp(fe, "0") == 0);
-    }
-    CLB Qb;   // first-order mode: cl_between_run_kernel's arguments, a run's CLN and the step map of cl_first_order_plan
-    if (fo_mode) {
-        std::memset(&Qb, 0, sizeof(Qb));
-        std::memcpy(Qb.A, am.A, sizeof(Qb.A));
-        std::memcpy(Qb.W, am.W, sizeof(Qb.W));
-        std::memcpy(Qb.MA, am.MA, sizeof(Qb.MA));
-        std::memcpy(Qb.MB, am.MB, sizeof(Qb.MB));
-    }
-    // guarded mode: the guard's bar (ALIPMPC_CL_GUARD_TOL: development, read per call) and its arguments — the eval
-    // hook's parameters on the scene the solves read
-    CLG Qg;
-    if (guarded) {
-        std::memset(&Qg, 0, sizeof(Qg));
-        Qg.tol = ALIPMPC_CL_GUARD_VIOL;
-        if (const char* ge = std::getenv("ALIPMPC_CL_GUARD_TOL")) {
-            char* end = nullptr;
-            const double v = std::strtod(ge, &end);
-            if (end != ge && *end == '\0' && !std::isnan(v)) Qg.tol = v;
-        }
-        Qg.kp = make_kp(h, B, false);
-    }
-    auto solves = [&](int i) { return !sch || ((sch->mask >> i) & 1ull) != 0; };
-    // first-order mode: does a tick of the step after tick i not solve (then tick i's solve leaves an anchor)
-    auto anchors = [&](int i) {
-        for (int j = i + 1; j < f_cyc; ++j)
-            if (!solves(j)) return true;
-        return false;
-    };
-    int live_step = -1;   // first-order mode: the step in which a solve tick last left anchors
-    const long long TT = (long long)S * f_cyc;
-    for (long long t = 0; t < TT;) {
-        const int s = (int)(t / f_cyc), i = (int)(t % f_cyc);
-        if (guarded && !solves(i) && live_step == s) {
-            // Guarded mode, after a solve of this step left anchors: one tick at a time, so that no episode runs two
-            // ticks' worth.  The episodes without an anchor run the nominal tick; the guard marks the anchored episodes
-            // whose u_fo fails the rows; the first-order kernel skips those; the solve tick's launches then act on them
-            // alone (cl_anchor_kernel clears the mark).  Every launch is issued whether or not an episode fired.
-            const double rest = T - i * (T / f_cyc);
-            const bool anchor = anchors(i);
-            for (int g = 0; g < G; ++g) {
-                CLP& Cg = grp[g].C;
-                const hipStream_t sg = grp[g].s;
-                Qn.C = Cg;
-                Qn.t0 = t;
-                Qn.nt = 1;
-                Qn.skip_anchored = 1;
-                Qn.plan_traj = grp[g].plan_traj;
-                hipLaunchKernelGGL(cl_nominal_run_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Qn);
-                HIPCHK(h, hipGetLastError());
-                const KP& Pg = grp[g].P;
-                Qg.kp.B = Cg.B;
-                Qg.kp.goal = Pg.goal; Qg.kp.cir = Pg.cir; Qg.kp.nc = Pg.nc; Qg.kp.elp = Pg.elp; Qg.kp.ne = Pg.ne;
-                Qg.flags = Cg.flags; Qg.x = Cg.x; Qg.pst = Cg.pst; Qg.hdv = Cg.hdv; Qg.leg = Cg.leg;
-                Qg.xa = grp[g].xa; Qg.ua = grp[g].ua; Qg.du = grp[g].du;
-                Qg.ch = Qn.rest[i][0]; Qg.shb = Qn.rest[i][1]; Qg.bsh = Qn.rest[i][2]; Qg.tt = Qn.rest[i][3];
-                HIPCHK(h, launch_guard(N, Qg, sg));
-                Qb.Q = Qn;
-                Qb.xa = grp[g].xa; Qb.ua = grp[g].ua; Qb.du = grp[g].du;
-                hipLaunchKernelGGL(cl_between_run_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Qb);
-                HIPCHK(h, hipGetLastError());
-                // the fired episodes' solve tick: the sensitivity build's launch on the group's queue pair
-                Cg.s = s;
-                Cg.i = i;
-                Cg.ch_r = std::cosh(beta * rest); Cg.shb_r = std::sinh(beta * rest) / beta;
-                Cg.bsh_r = std::sinh(beta * rest) * beta; Cg.tr = rest * (1.0 / T);
-                hipLaunchKernelGGL(cl_project_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Cg, 1);
-                HIPCHK(h, hipGetLastError());
-                KP Ps = Pg;
-                Ps.order = nullptr;
-                Ps.queue = h->dq + 2 * (Handle::NQ + g);
-                Ps.grad_out = grp[g].dfoot;
-                Ps.J_out = grp[g].du;
-                Ps.active_out = reinterpret_cast<int8_t*>(grp[g].ok);
-                HIPCHK(h, launch_sens(h, Ps, sg));
-                hipLaunchKernelGGL(cl_update_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Cg, 1);
-                HIPCHK(h, hipGetLastError());
-                if (grp[g].plan_traj) {
-                    hipLaunchKernelGGL(cl_plan_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Cg, grp[g].plan_traj, 1);
-                    HIPCHK(h, hipGetLastError());
-                }
-                CLA A;
-                std::memset(&A, 0, sizeof(A));
-                A.B = Cg.B; A.n = n; A.have = anchor ? 1 : 0; A.active = Cg.active; A.flags = Cg.flags;
-                A.xs = Cg.xs; A.u = Cg.u; A.ok = grp[g].ok; A.xa = grp[g].xa; A.ua = grp[g].ua;
-                hipLaunchKernelGGL(cl_anchor_kernel, dim3(grp[g].g1), dim3(256), 0, sg, A);
-                HIPCHK(h, hipGetLastError());
-            }
-            ++t;
-            continue;
-        }
-        if (!solves(i)) {   // a run of nominal ticks, possibly across step boundaries: one launch per group
-            // First-order mode, after a solve of this step left anchors: the run ends with the step (the anchor bits
-            // change there), its anchored episodes run cl_between_run_kernel and cl_nominal_run_kernel skips them.
-            // Before a step's first anchor no bit is set: the nominal launch alone, as in mode 0.
-            const bool live = live_step == s;
-            const long long tend = live ? (long long)(s + 1) * f_cyc : TT;
-            long long t1 = t + 1;
-            while (fuse && t1 < tend && !solves((int)(t1 % f_cyc))) ++t1;
-            for (int g = 0; g < G; ++g) {
-                Qn.C = grp[g].C;
-                Qn.t0 = t;
-                Qn.nt = (int)(t1 - t);
-                Qn.skip_anchored = live ? 1 : 0;
-                Qn.plan_traj = grp[g].plan_traj;
-                hipLaunchKernelGGL(cl_nominal_run_kernel, dim3(grp[g].g1), dim3(256), 0, grp[g].s, Qn);
-                HIPCHK(h, hipGetLastError());
-                if (live) {
-                    Qb.Q = Qn;
-                    Qb.xa = grp[g].xa; Qb.ua = grp[g].ua; Qb.du = grp[g].du;
-                    hipLaunchKernelGGL(cl_between_run_kernel, dim3(grp[g].g1), dim3(256), 0, grp[g].s, Qb);
-                    HIPCHK(h, hipGetLastError());
-                }
-            }
-            t = t1;
-            continue;
-        }
-        ++t;
-        {   // a solve tick, as alipmpc_closed_loop_batch always ran it
-            // rest_t = step_t - i * (step_t / f_cyc)   (main_sim_mpc.py:78)
-            const double rest = T - i * (T / f_cyc);
-            const bool anchor = fo_mode && anchors(i);
-            for (int g = 0; g < G; ++g) {
-                CLP& Cg = grp[g].C;
-                KP& Pg = grp[g].P;
-                const hipStream_t sg = grp[g].s;
-                Cg.s = s;
-                Cg.i = i;
-                Cg.ch_r = std::cosh(beta * rest); Cg.shb_r = std::sinh(beta * rest) / beta;
-                Cg.bsh_r = std::sinh(beta * rest) * beta; Cg.tr = rest * (1.0 / T);
-                hipLaunchKernelGGL(cl_project_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Cg, 0);
-                HIPCHK(h, hipGetLastError());
-                // wave program: after the first tick, solve last tick's long instances first (same bits per instance)
-                Pg.order = nullptr;
-                if (order_ok && (s > 0 || i > 0)) {
-                    hipLaunchKernelGGL(cl_order_kernel, dim3(1), dim3(CL_ORDER_THREADS), 0, sg, (const int32_t*)P.iters,
-                                       (const uint8_t*)C.active, (long long)B, ord);
-                    HIPCHK(h, hipGetLastError());
-                    Pg.order = ord;
-                }
-                // each group's own counter pair (after the ring): its launches run in order on its stream, and no
-                // other group or call can take the pair while one of them is in flight (ADVICE r4: ring pairs taken
-                // per tick let a group running ticks ahead land on a pair another group's launch still used)
-                Pg.queue = h->dq + 2 * (Handle::NQ + g);
-#ifdef ALIP_WSTAMP
-                {   // diagnostic record slots of this tick: (s f_cyc + i) B + instance
-                    const long long base = ((long long)s * f_cyc + i) * B;
-                    HIPCHK(h, hipMemcpyToSymbolAsync(HIP_SYMBOL(alip::g_wstamp_base), &base, sizeof(base), 0,
-                                                     hipMemcpyHostToDevice, sg));
-                    HIPCHK(h, hipStreamSynchronize(sg));   // &base is a stack value
-                }
-#endif
-                // first-order mode, a later tick of the step does not solve: the sensitivity build's launch (the solve's
-                // own bits, DESIGN.md §3.7) on the group's queue pair, du straight into the group's anchors
-                if (anchor) {
-                    KP Ps = Pg;
-                    Ps.order = nullptr;
-                    Ps.grad_out = grp[g].dfoot;
-                    Ps.J_out = grp[g].du;
-                    Ps.active_out = reinterpret_cast<int8_t*>(grp[g].ok);
-                    HIPCHK(h, launch_sens(h, Ps, sg));
-                } else {
-                    HIPCHK(h, launch_solve(h, Pg, sg, h->cl_split_it, h->cl_split_tr));
-                }
-                hipLaunchKernelGGL(cl_update_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Cg, 0);
-                HIPCHK(h, hipGetLastError());
-                if (grp[g].plan_traj) {
-                    hipLaunchKernelGGL(cl_plan_kernel, dim3(grp[g].g1), dim3(256), 0, sg, Cg, grp[g].plan_traj, 0);
-                    HIPCHK(h, hipGetLastError());
-                }
-                if (anchor || live_step == s) {   // (a live anchor bit is cleared by the step's first tick without one)
-                    CLA A;
-                    std::memset(&A, 0, sizeof(A));
-                    A.B = Cg.B; A.n = n; A.have = anchor ? 1 : 0; A.active = Cg.active; A.flags = Cg.flags;
-                    A.xs = Cg.xs; A.u = Cg.u; A.ok = grp[g].ok; A.xa = grp[g].xa; A.ua = grp[g].ua;
-                    hipLaunchKernelGGL(cl_anchor_kernel, dim3(grp[g].g1), dim3(256), 0, sg, A);
-                    HIPCHK(h, hipGetLastError());
-                }
-            }
-            live_step = anchor ? s : -1;
-        }
-    }
-    if (G > 1) {   // join
-        for (int g = 0; g < G; ++g) {
-            HIPCHK(h, hipEventRecord(h->gev[g], grp[g].s));
-            HIPCHK(h, hipStreamWaitEvent(st, h->gev[g], 0));
-        }
-    }
-    if (ds) {   // rows: scan the steps entered into row_start, then one wavefront per episode compacts its rows
-        hipLaunchKernelGGL(ds_scan_kernel, dim3(1), dim3(DS_SCAN_THREADS), 0, st, (const int32_t*)C.ds_nst,
-                           (long long)B, (int)f_cyc, d_rs);
-        HIPCHK(h, hipGetLastError());
-        if (ds_rows && ds->max_rows > 0) {
-            D.B = B; D.max_rows = ds->max_rows; D.S = S; D.f = f_cyc; D.nc_max = cf.nc_max; D.ne_max = cf.ne_max;
-            D.safe = ds->safe_dis; D.T = T; D.Td = T / f_cyc;
-            D.tick = C.ds_tick; D.step = C.ds_step; D.stt = C.status_traj;
-            D.cir = P.cir; D.nc = P.nc; D.elp = P.elp; D.ne = P.ne; D.goal = P.goal; D.row_start = d_rs;
-            constexpr int WPB = 256 / WAVE;
-            hipLaunchKernelGGL(ds_compact_kernel, dim3((unsigned)((B + WPB - 1) / WPB)), dim3(256), 0, st, D);
-            HIPCHK(h, hipGetLastError());
-        }
-    }
-    if (int e = span.end()) return e;
-    if (host && ds) {   // the total first: only the rows that exist (and fit) are copied back
-        std::vector<long long> rs(Bz + 1);
-        if (int e = Z.get(rs.data(), d_rs, (Bz + 1) * 8)) return e;
-        HIPCHK(h, hipStreamSynchronize(st));
-        if (ds->row_start) std::memcpy(ds->row_start, rs.data(), (Bz + 1) * 8);
-        const size_t nr = std::min<size_t>((size_t)rs[Bz], ds_cap);
-        if (nr && ds->X)
-            if (int e = Z.get(ds->X, D.X, nr * ncx * 8)) return e;
-        if (nr && ds->y_mpc)
-            if (int e = Z.get(ds->y_mpc, D.y_mpc, nr * 8 * 8)) return e;
-        if (nr && ds->y_act)
-            if (int e = Z.get(ds->y_act, D.y_act, nr * 8 * 8)) return e;
-        if (nr && ds->row_status)
-            if (int e = Z.get(ds->row_status, D.row_status, nr * 4)) return e;
-    }
-    return Z.finish();
-}
-
-int alipmpc_closed_loop_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc, double kick, uint64_t seed,
-                              const double* x0, const double* foot0, const double* goal, const int8_t* leg,
-                              const double* cir, const int32_t* nc, const double* elp, const int32_t* ne,
-                              double* foot_traj, double* x_traj, double* hd_traj, int32_t* status_traj,
-                              int32_t* iters_traj, int32_t* steps_to_goal, double* action_traj, void* hip_stream)
-{
-    return closed_loop_impl((Handle*)handle, B, S, f_cyc, kick, seed, x0, foot0, goal, leg, cir, nc, elp, ne, foot_traj,
-                            x_traj, hd_traj, status_traj, iters_traj, steps_to_goal, action_traj, hip_stream, nullptr);
-}
-
-int alipmpc_closed_loop_schedule_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc, uint64_t mpc_mask,
-                                       double kick, uint64_t seed,
-                                       const double* x0, const double* foot0, const double* goal, const int8_t* leg,
-                                       const double* cir, const int32_t* nc, const double* elp, const int32_t* ne,
-                                       double* foot_traj, double* x_traj, double* hd_traj, int32_t* status_traj,
-                                       int32_t* iters_traj, int32_t* steps_to_goal, double* action_traj,
-                                       double* plan_traj, void* hip_stream)
-{
-    const SchedArgs sch{mpc_mask, plan_traj};
-    return closed_loop_impl((Handle*)handle, B, S, f_cyc, kick, seed, x0, foot0, goal, leg, cir, nc, elp, ne, foot_traj,
-                            x_traj, hd_traj, status_traj, iters_traj, steps_to_goal, action_traj, hip_stream, nullptr,
-                            &sch);
-}
-
-int alipmpc_closed_loop_dataset_batch(void* handle, int64_t B, int32_t S, int32_t f_cyc, double kick, uint64_t seed,
-                                      const double* x0, const double* foot0, const double* goal, const int8_t* leg,
-                                      const double* cir, const int32_t* nc, const double* elp, const int32_t* ne,
-                                      double* foot_traj, double* x_traj, double* hd_traj, int32_t* status_traj,
-                                      int32_t* iters_traj, int32_t* steps_to_goal, double* action_traj,
-                                      int64_t first_index, double safe_dis, int64_t max_rows, double* X, double* y_mpc,
-                                      double* y_act, int32_t* row_status, int64_t* row_start, void* hip_stream)
-{
-    const DsArgs ds{first_index, safe_dis, max_rows, X, y_mpc, y_act, row_status, row_start};
-    return closed_loop_impl((Handle*)handle, B, S, f_cyc, kick, seed, x0, foot0, goal, leg, cir, nc, elp, ne, foot_traj,
-                            x_traj, hd_traj, status_traj, iters_traj, steps_to_goal, action_traj, hip_stream, &ds);
-}
+#include "closed_loop_host.inc"   // alipmpc_closed_loop_batch, _schedule_batch, _dataset_batch and their driver
 
 int32_t alipmpc_trace_len(const alipmpc_cfg* cfg)
 {

@@ -263,7 +263,7 @@ _M64 = (1 << 64) - 1
 
 def cl_uniform(seed, b, s, i, axis):
     """splitmix64 uniform [0, 1) of (episode, step, tick, axis): the closed loop's velocity kicks (the same
-    integer recipe as cl_uniform in csrc/alipmpc.hip)."""
+    integer recipe as cl_uniform in csrc/closed_loop.inc)."""
     key = ((((b * 1048576 + s) * 1024 + i) * 2 + axis) + 1) & _M64
     z = (seed + 0x9E3779B97F4A7C15 * key) & _M64
     z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
