@@ -1,10 +1,11 @@
 // alipmpc.hip — MI355X (gfx950) batched ALIP-MPC-CBF footstep planner: HIP kernels + the C ABI of
 // include/alipmpc.h.
 //
-// Files: this one holds the kernels, their parameter structs and launchers.  It includes fastmath.inc, resto_wave.inc
-// and lane_solve.inc (device code) and, into the host translation unit only, closed_loop.inc (the closed loop's kernels),
-// scenes.inc, dataset.inc, audit.inc (a kernel each), cl_ticks.inc (the closed loop's tick plan, plain C++) and
-// host_api.inc (all host code: constants, handle, argument staging, the extern "C" entry points; the closed loop's are
+// Files: this one holds the kernels and their parameter structs.  It includes fastmath.inc, resto_wave.inc and
+// lane_solve.inc (device code), solve_plan.inc (what a solve launches, plain C++) and launch.inc (the kernel launchers)
+// and, into the host translation unit only, closed_loop.inc (the closed loop's kernels), scenes.inc, dataset.inc,
+// audit.inc (a kernel each), cl_ticks.inc (the closed loop's tick plan, plain C++) and host_api.inc (all host code:
+// constants, handle, argument staging, the solve driver, the extern "C" entry points; the closed loop's are
 // closed_loop_host.inc, which it includes).
 //
 // What it replaces (reference /root/reference):
@@ -44,8 +45,9 @@
 #include <vector>
 
 #include "../../include/alipmpc.h"
+#include "solve_plan.inc"   // what a solve launches, and the row-step ladder of the solve kernels (plain C++)
 
-// Build partitioning (see the kernel launchers below): ALIP_PART = 0 host code, 1..6 one horizon each.
+// Build partitioning (see the kernel launchers, launch.inc): ALIP_PART = 0 host code, 1..6 one horizon each.
 #ifndef ALIP_PART
 #define ALIP_PART_HOST 1
 #define ALIP_PART_N(k) 1
@@ -176,7 +178,7 @@ __host__ __device__ constexpr long long cont_list(long long B, int cls, long lon
 }
 constexpr long long CONT_WORDS_PER_SLOT = 3;   // instance ids + the two class lists
 constexpr int PAIR_WAVES = 8;   // waves of a paired phase-2 workgroup: owners 0-3, fillers 4-7 (wave w and w + 4 share a SIMD)
-constexpr long long TEAM_CAP = 128;   // team workgroups of a phase-2 launch (team records beyond run one wave each)
+constexpr long long TEAM_CAP = SP_TEAM_CAP;   // team workgroups of a phase-2 launch (team records beyond run one wave each)
 // waves of a team-capable workgroup = members of a team, each testing one of that many consecutive line-search trials
 // per round.  r5 measured 8 against 4: the closed loop 33.8 vs 31.1 ms — every member also
 // runs the whole direction computation, and 8 of them share their SIMDs with the other episode group's phase 1
@@ -2692,7 +2694,7 @@ __device__ __forceinline__ void solve_one(const KP& P0, R* G, R* wsb, int wv, lo
     }
     if (status != ST_RESTO) break;
     if constexpr (sizeof(R) == 4) {   // fp32: the fp64 wave program solves this instance from its start (the
-        // stream's hand-off list, P.redo; launch() runs it after this launch).  The fp32 restoration phase took other
+        // stream's hand-off list, P.redo; launch_solve runs it after this launch).  The fp32 restoration phase took other
         // paths than the oracle's on the tolerance edges, and fp32's one lean build keeps every launch form
         // bit-identical.
         if (!P.redo) {   // (the host always provides the list; no write without one)
@@ -4810,378 +4812,7 @@ __global__ __launch_bounds__(256) void trace_kernel(TrP T)
 }
 #endif  // ALIP_PART_HOST
 
-// ------------------------------------------------------------------------------------------------
-// kernel launchers.  The library may be built as one translation unit per horizon N (ALIP_PART = N:
-// that horizon's kernels and launch_lip_N / launch_dd_N) plus ALIP_PART = 0 (host code, C ABI, rollout
-// kernels), compiled in parallel and linked into one .so; without ALIP_PART everything is one TU.
-// ------------------------------------------------------------------------------------------------
-// dynamic-LDS opt-in, once per kernel and size (hipFuncSetAttribute is a host round trip: keep it out of the
-// steady-state launch path)
-static void set_smem(const void* f, size_t smem)
-{
-    static std::mutex mtx;
-    static std::unordered_map<const void*, size_t> done[64];   // per device ordinal
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(mtx);
-    auto& d = done[dev & 63];
-    auto it = d.find(f);
-    if (it != d.end() && it->second >= smem) return;
-    // (r5a: at N = 6 this call failed for a kernel variant that was not launched — its workgroup's LDS above the CU's
-    // 160 KB — and the error it left was picked up by the launch's hipGetLastError, so every N = 6 solve reported
-    // "invalid argument".  A failure is consumed here; launching a kernel whose LDS does not fit fails on its own.)
-    if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
-        (void)hipGetLastError();
-        return;
-    }
-    d[f] = smem;
-}
-
-// workgroups of kernel f resident on the whole device at once (occupancy x CUs), cached per (f, smem)
-static unsigned resident_blocks(const void* f, size_t smem, int threads = WAVE * WAVES_PER_BLOCK)
-{
-    static std::mutex mtx;
-    static std::map<std::pair<const void*, size_t>, unsigned> cache[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(mtx);
-    auto& c = cache[dev & 63];
-    auto it = c.find({f, smem});
-    if (it != c.end()) return it->second;
-    int per_cu = 0, cus = 0;
-    unsigned r = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, threads, smem) == hipSuccess &&
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && per_cu > 0 && cus > 0)
-        r = (unsigned)per_cu * (unsigned)cus;
-    c[{f, smem}] = r;
-    return r;
-}
-
-// the team-capable build's workgroup LDS: smem (KP, G and WAVES_PER_BLOCK workspaces) with TEAM_WAVES workspaces
-template <int N, class R>
-size_t team_smem(size_t smem)
-{
-    const size_t fixed = sizeof(double) * (size_t)KP_DOUBLES + sizeof(R) * (size_t)Dim<N>::NG * Dim<N>::NCP;
-    return fixed + (smem - fixed) / WAVES_PER_BLOCK * TEAM_WAVES;
-}
-
-// the paired phase-2 build's workgroup LDS: PAIR_WAVES workspaces (fp64)
-template <int N>
-size_t pair_smem(size_t smem)
-{
-    const size_t fixed = sizeof(double) * ((size_t)KP_DOUBLES + (size_t)Dim<N>::NG * Dim<N>::NCP);
-    return fixed + (smem - fixed) / WAVES_PER_BLOCK * PAIR_WAVES;
-}
-// (compiled for the shapes with one row group per lane, the 2-waves-per-SIMD restoration-capable builds)
-constexpr bool pair_ksm(int ksm) { return 4 * ksm <= WAVE; }
-
-template <int N, class R>
-void launch_solve(const KP& P0, size_t smem, hipStream_t st, unsigned* res_out)
-{
-    const unsigned need = (unsigned)((P0.B + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-    // a split launch with team records (team-capable build, TEAM_WAVES-wave workgroups); phase 2: P0.team team
-    // workgroups ahead of the one-wave-per-instance ones
-    const unsigned need_t = (P0.resume ? (unsigned)P0.team : 0u) + (unsigned)((P0.B + TEAM_WAVES - 1) / TEAM_WAVES);
-    const size_t smem_t = team_smem<N, R>(smem);
-    // KSM = 4-row steps of the J layout, the smallest compiled size covering mo4 rows
-    auto go = [&](auto kq, auto k1, auto kt, auto kp) {
-        if constexpr (!std::is_same_v<decltype(kp), std::nullptr_t>) {
-            if (P0.resume == 2 && !res_out) {
-                // the paired phase 2 (alipmpc_create checked that its workgroup fits the LDS): the worst-case grid —
-                // ceil(np / 4) workgroups with pending records, then 8 regular records each, np + nr <= B
-                const size_t smem_p = pair_smem<N>(smem);
-                set_smem((const void*)kp, smem_p);
-                hipLaunchKernelGGL(kp, dim3((unsigned)((P0.B + 3) / 4) + 1u), dim3(WAVE * PAIR_WAVES), smem_p, st, P0);
-                return;
-            }
-        }
-        set_smem((const void*)kq, smem);
-        set_smem((const void*)k1, smem);
-        // (the team-capable build runs only where its workgroup fits the LDS: alipmpc_create clears the trial cuts
-        // otherwise)
-        if (smem_t <= 160 * 1024) set_smem((const void*)kt, smem_t);
-        const unsigned res = resident_blocks((const void*)kq, smem);
-        if (res_out) {   // query only (alipmpc_solve_slots)
-            *res_out = res;
-            return;
-        }
-        if (res > 0 && (need > res || P0.bcount) && !P0.resume)   // the persistent work queue over the resident workgroups
-            hipLaunchKernelGGL(kq, dim3(res), dim3(WAVE * WAVES_PER_BLOCK), smem, st, P0);
-        else if (P0.team > 0)        // a split launch with team records: both phases on the team-capable build
-            hipLaunchKernelGGL(kt, dim3(need_t > 0 ? need_t : 1u), dim3(WAVE * TEAM_WAVES), smem_t, st, P0);
-        else                         // every instance has a resident wave: one instance per wave
-            hipLaunchKernelGGL(k1, dim3(need > 0 ? need : 1u), dim3(WAVE * WAVES_PER_BLOCK), smem, st, P0);
-    };
-    // the team-capable build exists in fp64 only: in fp32 its different code rounded differently from the plain build's
-    // (fp32 contraction / packing decisions depend on the surrounding code), so fp32 splits never make team records
-    // cfg.restoration = IPOPT: the restoration-capable builds, except for phase 1 of a split launch (records: a pending
-    // restoration is cut to phase 2); the query of the resident slots uses the lean work-queue build either way
-    // (fp32 has the lean build only: a failed search hands the instance to the fp64 wave program)
-    const bool rs = P0.resto_ipopt && !(P0.ckpt && !P0.resume) && !res_out;
-#define ALIP_GO(K)                                                                                              \
-    do {                                                                                                        \
-        if constexpr (sizeof(R) == 8) {                                                                         \
-            if (rs) {                                                                                           \
-                if constexpr (pair_ksm(K))                                                                      \
-                    go(solve_kernel<N, K, R, false, false, true>, solve_kernel<N, K, R, true, false, true>,     \
-                       solve_kernel<N, K, R, true, true, true>, solve_kernel<N, K, R, true, false, true, true>); \
-                else                                                                                            \
-                    go(solve_kernel<N, K, R, false, false, true>, solve_kernel<N, K, R, true, false, true>,     \
-                       solve_kernel<N, K, R, true, true, true>, nullptr);                                       \
-            } else                                                                                              \
-                go(solve_kernel<N, K, R, false>, solve_kernel<N, K, R, true>, solve_kernel<N, K, R, true, true>, \
-                   nullptr);                                                                                    \
-        } else {                                                                                                \
-            go(solve_kernel<N, K, R, false>, solve_kernel<N, K, R, true>, solve_kernel<N, K, R, true, false>,   \
-               nullptr);                                                                                        \
-        }                                                                                                       \
-    } while (0)
-#ifdef ALIP_DEV_ONLY_KSM   // dev builds for register reports (tools/regs.py): one row-step count only
-    ALIP_GO(ALIP_DEV_ONLY_KSM);
-#else
-    if (P0.mo4 <= 16)   // (r5: sig_step / modi with no obstacle slots at N <= 3, cfg1: 0.1255 -> 0.1195 ms)
-        ALIP_GO(4);
-    else if (P0.mo4 <= 32)
-        ALIP_GO(8);
-    else if (P0.mo4 <= 40)
-        ALIP_GO(10);
-    else if (P0.mo4 <= 48)
-        ALIP_GO(12);
-    else if (P0.mo4 <= 64)
-        ALIP_GO(16);
-    else if (P0.mo4 <= 96)
-        ALIP_GO(24);
-    else if (P0.mo4 <= 128)
-        ALIP_GO(32);
-    else
-        ALIP_GO(48);
-#endif
-#undef ALIP_GO
-}
-
-// the sensitivity build (fp64, N <= 5: n <= 15, the gj_regs domain): the persistent work queue over at most the
-// resident workgroups, whatever B is
-template <int N>
-hipError_t launch_sens_t(const KP& P0, size_t smem, hipStream_t st, bool obs)
-{
-    if constexpr (Dim<N>::n > ALIP_GJ_MAX_N || Dim<N>::n > 15) {
-        return hipErrorNotSupported;
-    } else {
-        auto go = [&](auto kq) {
-            set_smem((const void*)kq, smem);
-            const unsigned res = resident_blocks((const void*)kq, smem);
-            const unsigned need = (unsigned)((P0.B + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-            const unsigned grid = res > 0 && res < need ? res : (need > 0 ? need : 1u);
-            hipLaunchKernelGGL(kq, dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), smem, st, P0);
-        };
-#define ALIP_GO(K)                                 \
-    do {                                           \
-        if (obs && P0.resto_ipopt)                 \
-            go(sens_obs_kernel<N, K, true>);       \
-        else if (obs)                              \
-            go(sens_obs_kernel<N, K, false>);      \
-        else if (P0.resto_ipopt)                   \
-            go(sens_kernel<N, K, true>);           \
-        else                                       \
-            go(sens_kernel<N, K, false>);          \
-    } while (0)
-        if (P0.mo4 <= 16)
-            ALIP_GO(4);
-        else if (P0.mo4 <= 32)
-            ALIP_GO(8);
-        else if (P0.mo4 <= 40)
-            ALIP_GO(10);
-        else if (P0.mo4 <= 48)
-            ALIP_GO(12);
-        else if (P0.mo4 <= 64)
-            ALIP_GO(16);
-        else if (P0.mo4 <= 96)
-            ALIP_GO(24);
-        else if (P0.mo4 <= 128)
-            ALIP_GO(32);
-        else
-            ALIP_GO(48);
-#undef ALIP_GO
-        return hipGetLastError();
-    }
-}
-
-// solve kernels run in the handle's precision (cfg.precision); the eval hook is always fp64
-template <int N>
-hipError_t launch_t(bool solve, bool f32, const KP& P, size_t smem, hipStream_t st, unsigned* res_out)
-{
-    if (solve && f32) {
-#ifndef ALIP_DEV_ONLY_KSM
-        launch_solve<N, float>(P, smem, st, res_out);
-#endif
-    } else if (solve) {
-        launch_solve<N, double>(P, smem, st, res_out);
-    } else {
-        // grid-stride eval kernel (16 instances per workgroup): at most the resident workgroups
-        set_smem((const void*)eval_kernel<N>, smem);
-        const unsigned need = (unsigned)((P.B + GROUPS_PER_BLOCK - 1) / GROUPS_PER_BLOCK);
-        const unsigned res = resident_blocks((const void*)eval_kernel<N>, smem);
-        const unsigned egrid = res > 0 && res < need ? res : (need > 0 ? need : 1u);
-        hipLaunchKernelGGL(eval_kernel<N>, dim3(egrid), dim3(WAVE * WAVES_PER_BLOCK), smem, st, P);
-    }
-    return hipGetLastError();
-}
-
-template <int N>
-hipError_t launch_dd(bool solve, const KP& P, size_t smem, hipStream_t st)
-{
-    const unsigned grid = (unsigned)((P.B + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-    auto go = [&](auto kern) {
-        set_smem((const void*)kern, smem);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), smem, st, P);
-    };
-    if (!solve)
-        go(dd_eval_kernel<N>);
-    else if (P.mo4 <= WAVE)
-        go(dd_solve_kernel<N, 1>);
-    else if (P.mo4 <= 2 * WAVE)
-        go(dd_solve_kernel<N, 2>);
-    else
-        go(dd_solve_kernel<N, 3>);
-    return hipGetLastError();
-}
-
-#define ALIP_LAUNCHERS(k)                                                                              \
-    hipError_t launch_lip_##k(bool solve, bool f32, const KP& P, size_t smem, hipStream_t st,          \
-                              unsigned* res_out)                                                       \
-    {                                                                                                  \
-        return launch_t<k>(solve, f32, P, smem, st, res_out);                                          \
-    }                                                                                                  \
-    hipError_t launch_dd_##k(bool solve, const KP& P, size_t smem, hipStream_t st)                     \
-    {                                                                                                  \
-        return launch_dd<k>(solve, P, smem, st);                                                       \
-    }                                                                                                  \
-    hipError_t launch_sens_##k(const KP& P, size_t smem, hipStream_t st, bool obs)                     \
-    {                                                                                                  \
-        return launch_sens_t<k>(P, smem, st, obs);                                                     \
-    }
-#define ALIP_LAUNCH_DECL(k)                                                                            \
-    hipError_t launch_lip_##k(bool solve, bool f32, const KP& P, size_t smem, hipStream_t st,          \
-                              unsigned* res_out = nullptr);                                            \
-    hipError_t launch_dd_##k(bool solve, const KP& P, size_t smem, hipStream_t st);                    \
-    hipError_t launch_sens_##k(const KP& P, size_t smem, hipStream_t st, bool obs = false);
-ALIP_LAUNCH_DECL(1) ALIP_LAUNCH_DECL(2) ALIP_LAUNCH_DECL(3) ALIP_LAUNCH_DECL(4) ALIP_LAUNCH_DECL(5) ALIP_LAUNCH_DECL(6)
-#if ALIP_PART_N(1)
-ALIP_LAUNCHERS(1)
-#endif
-#if ALIP_PART_N(2)
-ALIP_LAUNCHERS(2)
-#endif
-#if ALIP_PART_N(3)
-ALIP_LAUNCHERS(3)
-#endif
-#if ALIP_PART_N(4)
-ALIP_LAUNCHERS(4)
-#endif
-#if ALIP_PART_N(5)
-ALIP_LAUNCHERS(5)
-#endif
-#if ALIP_PART_N(6)
-ALIP_LAUNCHERS(6)
-#endif
-
-// lane solver (lane_solve.inc): N = 3, NC = compiled circle slots (>= cfg.nc_max), or (nct = LANE_FORM5, modi) the
-// form build's 5 obstacle-form slots (circles and ellipses, >= cfg.nc_max + cfg.ne_max).  A persistent
-// grid of at most the resident one-wave workgroups; each lane takes instances from the launch's work queue.
-constexpr int LANE_FORM5 = 100 + 5;
-template <int N, int NC, bool MODI, class R, bool FM = false>
-void launch_lane_t(const KP& P, hipStream_t st, unsigned* res_out)
-{
-    auto kern = lane_kernel<N, NC, MODI, typename std::conditional<FM, lane::Form<R>, R>::type>;
-    const unsigned res = resident_blocks((const void*)kern, 0, WAVE);
-    if (res_out) {
-        *res_out = res;
-        return;
-    }
-    const unsigned need = (unsigned)((P.B + WAVE - 1) / WAVE);
-    // small batches are spread over every resident wave (the kernel's first fetch takes ceil(B / grid))
-    const unsigned grid = res > 0 ? res : (need > 0 ? need : 1u);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE), 0, st, P);
-}
-template <class R>
-hipError_t launch_lane_r(int nct, bool modi, const KP& P, hipStream_t st, unsigned* res_out)
-{
-    if (modi) {
-        if (nct == 0) launch_lane_t<3, 0, true, R>(P, st, res_out);
-        else if (nct == 5) launch_lane_t<3, 5, true, R>(P, st, res_out);
-        else if (nct == 6) launch_lane_t<3, 6, true, R>(P, st, res_out);
-        else if (nct == LANE_FORM5) launch_lane_t<3, 5, true, R, true>(P, st, res_out);
-        else return hipErrorInvalidValue;
-    } else {
-        if (nct == 0) launch_lane_t<3, 0, false, R>(P, st, res_out);
-        else if (nct == 5) launch_lane_t<3, 5, false, R>(P, st, res_out);
-        else if (nct == 6) launch_lane_t<3, 6, false, R>(P, st, res_out);
-        else return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-hipError_t launch_lane_f64(int nct, bool modi, const KP& P, hipStream_t st, unsigned* res_out);
-hipError_t launch_lane_f32(int nct, bool modi, const KP& P, hipStream_t st, unsigned* res_out);
-#if !defined(ALIP_PART) || ALIP_PART == 7
-hipError_t launch_lane_f64(int nct, bool modi, const KP& P, hipStream_t st, unsigned* res_out)
-{
-    return launch_lane_r<double>(nct, modi, P, st, res_out);
-}
-#endif
-#if !defined(ALIP_PART) || ALIP_PART == 8
-hipError_t launch_lane_f32(int nct, bool modi, const KP& P, hipStream_t st, unsigned* res_out)
-{
-    return launch_lane_r<float>(nct, modi, P, st, res_out);
-}
-#endif
-
-// sweep kernel (eval hook, N = 3, circles only): CH-instance chunks per wave, WPG waves per workgroup, a grid-stride
-// over the chunks on at most the resident workgroups
-hipError_t launch_sweep(int nc, bool fen, const KP& P, hipStream_t st);
-#if ALIP_PART_N(3)
-template <int NC, bool FEN, int CH, int WPG>
-void launch_sweep_t(const KP& P, hipStream_t st)
-{
-    using L = SweepL<NC, FEN>;
-    auto kern = sweep_kernel<NC, FEN, CH, WPG>;
-    const size_t smem = sizeof(double) * ((size_t)L::GL + (size_t)WPG * (CH / 2) * L::SLOTD);
-    set_smem((const void*)kern, smem);
-    const unsigned res = resident_blocks((const void*)kern, smem, WAVE * WPG);
-    const long long per = (long long)CH * WPG;
-    const unsigned need = (unsigned)((P.B + per - 1) / per);
-    const unsigned grid = res > 0 && res < need ? res : (need > 0 ? need : 1u);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE * WPG), smem, st, P);
-}
-template <int NC, bool FEN>
-void launch_sweep_s(const KP& P, hipStream_t st)
-{
-    // instances per wave x waves per workgroup (LDS: the G/E copy per workgroup + CH/2 coefficient slots per
-    // wave); ALIPMPC_SWEEP_SHAPE (dev A/B) picks another shape
-    const char* se = getenv("ALIPMPC_SWEEP_SHAPE");
-    const int shape = se ? atoi(se) : SWEEP_SHAPE_DEFAULT;
-    // measured (profiles/r2/sweep/shapes.txt, B = 65,536): 64 x 1 0.0837 ms (one wave per SIMD: the LDS of a
-    // 64-instance chunk), 32 x 2 0.0759 ms (two per SIMD, 2048 waves), 16 x 4 0.106 ms (232 VGPRs cap the SIMD at
-    // two waves, and each wave repeats the set-up for a quarter of the instances)
-    if (shape == 641)
-        launch_sweep_t<NC, FEN, 64, 1>(P, st);
-    else
-        launch_sweep_t<NC, FEN, 32, 2>(P, st);
-}
-hipError_t launch_sweep(int nc, bool fen, const KP& P, hipStream_t st)
-{
-#define SWCASE(K)                                              \
-    case K:                                                    \
-        fen ? launch_sweep_s<K, true>(P, st) : launch_sweep_s<K, false>(P, st); \
-        break;
-    switch (nc) {
-        SWCASE(0) SWCASE(1) SWCASE(2) SWCASE(3) SWCASE(4) SWCASE(5) SWCASE(6)
-    default:
-        return hipErrorInvalidValue;
-    }
-#undef SWCASE
-    return hipGetLastError();
-}
-#endif
+#include "launch.inc"   // the kernel launchers, in every translation unit
 
 #if ALIP_PART_HOST
 // ------------------------------------------------------------------------------------------------

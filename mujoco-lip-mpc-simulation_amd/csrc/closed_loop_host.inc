@@ -408,9 +408,9 @@ static int cl_solve_tick(ClLoop& L, int g, const ClSeg& seg, const ClRest& r, bo
         Ps.grad_out = gr.an.dfoot;
         Ps.J_out = gr.an.du;
         Ps.active_out = reinterpret_cast<int8_t*>(gr.an.ok);
-        HIPCHK(h, launch_sens(h, Ps, sg));
+        HIPCHK(h, launch_solve(h, Ps, sg, SP_PROG_SENS));
     } else {
-        HIPCHK(h, launch_solve(h, Ps, sg, h->cl_split_it, h->cl_split_tr));
+        HIPCHK(h, launch_solve(h, Ps, sg, program_of(h), h->cl_split_it, h->cl_split_tr));
     }
     hipLaunchKernelGGL(cl_update_kernel, dim3(gr.g1), dim3(256), 0, sg, Cg, fo);
     HIPCHK(h, hipGetLastError());

@@ -47,6 +47,9 @@ struct Handle {
     // the paired phase 2 of the batch API's split (ALIPMPC_SPLIT_PAIR=0 turns it off): fp64 wave program with
     // cfg.restoration = IPOPT, one row group per lane, 8 workspaces within the LDS; only without team records
     bool split_pair = false;
+    // the wave program's resident slots, lean and restoration-capable work-queue build, taken on first use
+    // (resident_slots; -1: not yet)
+    mutable std::atomic<long long> slots_c[2] = {{-1}, {-1}};
     // Record buffers are sized ONCE for the resident slots (the largest batch that splits) and never reallocated or
     // freed before alipmpc_destroy, so a graph captured on a stream keeps a valid pointer whatever batch sizes run on
     // that stream later.  At most SPLIT_STREAMS of them: a further stream runs the one-phase form.
@@ -305,29 +308,18 @@ int lane_slots_for(const alipmpc_cfg& c)
 
 size_t smem_bytes(const Handle* h, bool solve, int force_f64 = 0)
 {
-    if (h->cfg.variant == ALIPMPC_VARIANT_DD) {
-        int wsd = 0;
-        switch (h->N) {
-#define DDCASE(NN) \
-    case NN: wsd = ddw_doubles<NN>(h->cfg.nc_max + h->cfg.ne_max, h->mo4); break;
-            DDCASE(1) DDCASE(2) DDCASE(3) DDCASE(4) DDCASE(5) DDCASE(6)
-#undef DDCASE
-        }
-        (void)solve;
+    const alipmpc_cfg& c = h->cfg;
+    if (c.variant == ALIPMPC_VARIANT_DD) {
+        const int wsd = with_n(h->N, 0, [&](auto n) { return ddw_doubles<decltype(n)::value>(c.nc_max + c.ne_max, h->mo4); });
         return sizeof(double) * ((size_t)KP_DOUBLES + (size_t)WAVES_PER_BLOCK * wsd);
     }
-    const bool f32 = solve && h->cfg.precision == ALIPMPC_PREC_FP32 && !force_f64;
-    int wsd = 0;
-    switch (h->N) {
-#define WSCASE(NN)                                                                                     \
-    case NN:                                                                                           \
-        wsd = solve ? (f32 ? wss_elems<NN, float>(h->cfg.nc_max, h->cfg.ne_max, h->mr4_s, h->mo4)      \
-                           : wss_elems<NN, double>(h->cfg.nc_max, h->cfg.ne_max, h->mr4_s, h->mo4)) \
-                    : gws_doubles<NN>(h->cfg.nc_max, h->cfg.ne_max, h->mr4);                           \
-        break;
-        WSCASE(1) WSCASE(2) WSCASE(3) WSCASE(4) WSCASE(5) WSCASE(6)
-#undef WSCASE
-    }
+    const bool f32 = solve && c.precision == ALIPMPC_PREC_FP32 && !force_f64;
+    const int wsd = with_n(h->N, 0, [&](auto n) {
+        constexpr int NN = decltype(n)::value;
+        return solve ? (f32 ? wss_elems<NN, float>(c.nc_max, c.ne_max, h->mr4_s, h->mo4)
+                            : wss_elems<NN, double>(c.nc_max, c.ne_max, h->mr4_s, h->mo4))
+                     : gws_doubles<NN>(c.nc_max, c.ne_max, h->mr4);
+    });
     const int e = solve ? 0 : h->NG * 5 + ((h->NG * 5) & 1);   // (solve_kernel: E from global memory)
     const int ncp = solve ? h->NCP : h->NCPU;
     // KP in fp64 units, then G, E and the per-wave workspaces in the kernel's arithmetic type
@@ -381,15 +373,6 @@ KP make_kp(const Handle* h, long long B, bool solve)
     return P;
 }
 
-// J-layout steps (4 rows each) of the compiled solve kernels; mo4 is rounded up to 4 * ksm_of(rows)
-int ksm_of(int rows)
-{
-    static const int K[] = {4, 8, 10, 12, 16, 24, 32, 48};
-    for (int k : K)
-        if (rows <= 4 * k) return k;
-    return 1 << 20;
-}
-
 // cfg.restoration = IPOPT, fp32 programs and the lane program: the stream's hand-off list ([0] = count, then the
 // instances), allocated outside a capture (a capture needs an uncaptured solve of at least its B on the stream first).
 // A list too small for B is retired to Handle::redo_retired, where it stays allocated until alipmpc_destroy: launches
@@ -414,92 +397,43 @@ static hipError_t redo_list(const Handle* h, hipStream_t st, long long B, uint32
     return hipSuccess;
 }
 
-// the listed instances, solved from their start by the fp64 wave program's restoration-capable work queue (slot k
-// solves redo[1 + k], k < redo[0]) on the same stream
-static hipError_t launch_handoff(const Handle* h, const KP& P, const uint32_t* redo, hipStream_t st)
+// the eval hook's launch: DD's kernel, the sweep kernel where the handle has one, or the grid-stride eval kernel
+hipError_t launch_eval_hook(const Handle* h, const KP& P, hipStream_t st)
 {
-    KP Q = P;
-    Q.redo = nullptr;
-    Q.order = reinterpret_cast<const int32_t*>(redo + 1);
-    Q.bcount = redo;
-    Q.ckpt = nullptr;
-    Q.cont = nullptr;
-    Q.resume = 0;
-    Q.team = 0;
-    Q.ckpt_it = 0;
-    Q.ckpt_tr = 0;
-    const size_t sm = smem_bytes(h, true, 1);
-    switch (h->N) {
-    case 1: return launch_lip_1(true, false, Q, sm, st, nullptr);
-    case 2: return launch_lip_2(true, false, Q, sm, st, nullptr);
-    case 3: return launch_lip_3(true, false, Q, sm, st, nullptr);
-    case 4: return launch_lip_4(true, false, Q, sm, st, nullptr);
-    case 5: return launch_lip_5(true, false, Q, sm, st, nullptr);
-    case 6: return launch_lip_6(true, false, Q, sm, st, nullptr);
-    }
-    return hipErrorInvalidValue;
+    const size_t smem = smem_bytes(h, false);
+    if (h->cfg.variant == ALIPMPC_VARIANT_DD)
+        return with_n(h->N, hipErrorInvalidValue, [&](auto n) { return launch_dd<decltype(n)::value>(false, P, smem, st); });
+    if (h->sweep_nc >= 0) return launch_sweep(h->sweep_nc, h->cfg.variant == ALIPMPC_VARIANT_MODI, P, st);
+    return with_n(h->N, hipErrorInvalidValue, [&](auto n) { return launch_eval<decltype(n)::value>(P, smem, st); });
 }
 
-// res_out != null: no launch, report the resident workgroups of the solve kernel (0 for DD: no queue)
-hipError_t launch(const Handle* h, bool solve, const KP& P, hipStream_t st, unsigned* res_out = nullptr)
+// the program a solve of the handle runs (solve_plan.inc)
+SpProgram program_of(const Handle* h)
 {
-    const size_t smem = smem_bytes(h, solve);
-    const bool f32 = h->cfg.precision == ALIPMPC_PREC_FP32;
-    if (h->cfg.variant == ALIPMPC_VARIANT_DD && res_out) {
-        *res_out = 0;
-        return hipSuccess;
+    return h->cfg.variant == ALIPMPC_VARIANT_DD ? SP_PROG_DD : h->lane_nct >= 0 ? SP_PROG_LANE
+         : h->cfg.precision == ALIPMPC_PREC_FP32 ? SP_PROG_WAVE_F32 : SP_PROG_WAVE_F64;
+}
+
+// instances resident at once on the handle's work-queue solve kernel (alipmpc_solve_slots; 0 for DD: no queue); resto:
+// on the wave program's restoration-capable build
+long long resident_slots(const Handle* h, bool resto = false)
+{
+    const bool f32 = h->cfg.precision == ALIPMPC_PREC_FP32, modi = h->cfg.variant == ALIPMPC_VARIANT_MODI;
+    switch (program_of(h)) {
+    case SP_PROG_DD: return 0;
+    case SP_PROG_LANE:
+        return f32 ? (long long)lane_resident<float>(h->lane_nct, modi) * lane::lanes_of<float>()
+                   : (long long)lane_resident<double>(h->lane_nct, modi) * lane::lanes_of<double>();
+    default: break;
     }
-    if (h->cfg.variant == ALIPMPC_VARIANT_DD) {
-        switch (h->N) {
-        case 1: return launch_dd_1(solve, P, smem, st);
-        case 2: return launch_dd_2(solve, P, smem, st);
-        case 3: return launch_dd_3(solve, P, smem, st);
-        case 4: return launch_dd_4(solve, P, smem, st);
-        case 5: return launch_dd_5(solve, P, smem, st);
-        case 6: return launch_dd_6(solve, P, smem, st);
-        }
-        return hipErrorInvalidValue;
+    long long s = h->slots_c[resto].load(std::memory_order_relaxed);
+    if (s < 0) {
+        const size_t smem = smem_bytes(h, true);
+        s = (long long)WAVES_PER_BLOCK *
+            with_n(h->N, 0u, [&](auto n) { return wave_resident<decltype(n)::value>(f32, resto, h->mo4, smem); });
+        h->slots_c[resto].store(s, std::memory_order_relaxed);
     }
-    if (!solve && h->sweep_nc >= 0) {
-        if (res_out) return hipErrorInvalidValue;
-        return launch_sweep(h->sweep_nc, h->cfg.variant == ALIPMPC_VARIANT_MODI, P, st);
-    }
-    if (solve && h->lane_nct >= 0) {
-        const bool modi = h->cfg.variant == ALIPMPC_VARIANT_MODI;
-        if (res_out || !P.resto_ipopt)
-            return f32 ? launch_lane_f32(h->lane_nct, modi, P, st, res_out) : launch_lane_f64(h->lane_nct, modi, P, st, res_out);
-        // cfg.restoration = IPOPT: the lane program solves every instance whose line searches all succeed; an instance
-        // whose search fails is listed (P.redo) and solved from its start by the fp64 wave program's restoration-capable
-        // work queue, on the same stream (the same queue pair: the lane kernel's last wave resets it)
-        KP P1 = P;
-        if (hipError_t e = redo_list(h, st, P.B, &P1.redo)) return e;
-        if (hipError_t e = hipMemsetAsync(P1.redo, 0, sizeof(uint32_t), st)) return e;
-        if (hipError_t e = f32 ? launch_lane_f32(h->lane_nct, modi, P1, st, nullptr)
-                               : launch_lane_f64(h->lane_nct, modi, P1, st, nullptr))
-            return e;
-        return launch_handoff(h, P, P1.redo, st);
-    }
-    if (solve && f32 && P.resto_ipopt && !res_out && !P.redo) {
-        // the fp32 wave program, cfg.restoration = IPOPT: the same hand-off (solve_one lists an instance whose search
-        // fails).  Phase 1 of a split launch starts the list and phase 2 continues it; the fp64 work queue runs after
-        // the last launch of the solve.
-        KP P1 = P;
-        if (hipError_t e = redo_list(h, st, P.B, &P1.redo)) return e;
-        if (!P.resume)
-            if (hipError_t e = hipMemsetAsync(P1.redo, 0, sizeof(uint32_t), st)) return e;
-        if (hipError_t e = launch(h, true, P1, st)) return e;
-        if (P.ckpt && !P.resume) return hipSuccess;
-        return launch_handoff(h, P, P1.redo, st);
-    }
-    switch (h->N) {
-    case 1: return launch_lip_1(solve, f32, P, smem, st, res_out);
-    case 2: return launch_lip_2(solve, f32, P, smem, st, res_out);
-    case 3: return launch_lip_3(solve, f32, P, smem, st, res_out);
-    case 4: return launch_lip_4(solve, f32, P, smem, st, res_out);
-    case 5: return launch_lip_5(solve, f32, P, smem, st, res_out);
-    case 6: return launch_lip_6(solve, f32, P, smem, st, res_out);
-    }
-    return hipErrorInvalidValue;
+    return s;
 }
 
 // hip_stream argument -> the stream to launch on (NULL = host-pointer mode on the handle's own stream,
@@ -930,22 +864,11 @@ int alipmpc_create(const alipmpc_cfg* cfg, int device, void** handle)
     }
     // team records need the team-capable build's TEAM_WAVES workspaces in one workgroup: without room, no trial cut
     if (cfg->variant != ALIPMPC_VARIANT_DD && cfg->precision != ALIPMPC_PREC_FP32 && h->lane_nct < 0) {
-        size_t st_ = 0;
-        switch (h->N) {
-#define TSCASE(NN) \
-    case NN: st_ = team_smem<NN, double>(smem_bytes(h, true)); break;
-            TSCASE(1) TSCASE(2) TSCASE(3) TSCASE(4) TSCASE(5) TSCASE(6)
-#undef TSCASE
-        }
+        const size_t sm = smem_bytes(h, true);
+        const size_t st_ = with_n(h->N, (size_t)0, [&](auto n) { return team_smem<decltype(n)::value, double>(sm); });
         if (st_ > 160 * 1024) h->split_tr = h->cl_split_tr = 0;
         // the paired phase 2 (solve_kernel<..., PR>): where its 8 workspaces fit; it has a cut of its own
-        size_t sp_ = 0;
-        switch (h->N) {
-#define PSCASE(NN) \
-    case NN: sp_ = pair_smem<NN>(smem_bytes(h, true)); break;
-            PSCASE(1) PSCASE(2) PSCASE(3) PSCASE(4) PSCASE(5) PSCASE(6)
-#undef PSCASE
-        }
+        const size_t sp_ = with_n(h->N, (size_t)0, [&](auto n) { return pair_smem<decltype(n)::value>(sm); });
         const char* pe = std::getenv("ALIPMPC_SPLIT_PAIR");
         h->split_pair = !(pe && std::atoi(pe) == 0) && cfg->restoration == ALIPMPC_RESTORATION_IPOPT &&
                         pair_ksm(h->mo4 / 4) && sp_ <= 160 * 1024;
@@ -962,16 +885,6 @@ int alipmpc_create(const alipmpc_cfg* cfg, int device, void** handle)
 // 30-iteration cap, DESIGN.md) otherwise finish at the pace of the busiest SIMDs, which hold two or three of them
 // among their four waves; in phase 2 they are few enough for a SIMD each.  Every instance executes the same
 // arithmetic either way (the record holds its exact loop state): same bits (test_split_launch_bit_identical).
-// whether a solve of B instances with these cuts runs as a split launch (launch_solve and alipmpc_solve_launches share
-// it): the wave program (not DD), an iteration cut or — fp64, the team-capable build — a trial cut, B within the slots
-static bool split_form(const Handle* h, long long B, int split_it, int split_tr, long long slots)
-{
-    const alipmpc_cfg& cf = h->cfg;
-    if (cf.precision == ALIPMPC_PREC_FP32) split_tr = 0;   // (the team-capable build is fp64 only)
-    return cf.variant != ALIPMPC_VARIANT_DD && h->lane_nct < 0 && (split_it > 0 || split_tr > 0) && B >= 2 &&
-           B <= slots;
-}
-
 // the stream's record buffer (Handle::split), sized for `slots` instances; nullptr: run the one-phase form
 static void* split_buffer(Handle* h, hipStream_t st, size_t need, hipError_t& err)
 {
@@ -1006,41 +919,104 @@ static void* split_buffer(Handle* h, hipStream_t st, size_t need, hipError_t& er
     return it->second.p;
 }
 
-// pair: the paired phase 2 where it applies (the batch API; the closed loop's per-tick solves keep the 4-wave form)
-static hipError_t launch_solve(Handle* h, const KP& P, hipStream_t st, int split_it, int split_tr, bool pair = false)
+// what solve_plan is told about a solve of the handle's B = P.B instances: the program (a sensitivity solve names its
+// own), the cuts, and pair, whether the caller takes the paired phase 2 (the batch API; the closed loop's per-tick
+// solves keep the 4-wave form).  The record buffer is the driver's to add.
+static SpFacts solve_facts(const Handle* h, SpProgram prog, long long B, bool ordered, int split_it, int split_tr, bool pair)
 {
-    const alipmpc_cfg& cf = h->cfg;
-    if (cf.precision == ALIPMPC_PREC_FP32) split_tr = 0;   // (the team-capable build is fp64 only)
-    if (!split_form(h, P.B, split_it, split_tr, 1ll << 62) || P.order) return launch(h, true, P, st);
-    unsigned res = 0;
-    if (hipError_t e = launch(h, true, P, st, &res)) return e;
-    const long long slots = (long long)res * WAVES_PER_BLOCK;
-    if (slots < P.B) return launch(h, true, P, st);   // the work-queue form
-    // records for the slots, not for this B: the buffer of a stream never changes size
-    const size_t rec_bytes = ((size_t)slots * ckpt_doubles(h->mo4) * sizeof(double) + 255) & ~(size_t)255;
-    const size_t hdr = (size_t)cont_hdr(slots);
-    // (instance ids and the two class lists of the single records)
-    const size_t need = rec_bytes + (hdr + (size_t)CONT_WORDS_PER_SLOT * (size_t)slots) * sizeof(uint32_t);
-    hipError_t berr = hipSuccess;
-    void* buf = split_buffer(h, st, need, berr);
-    if (berr != hipSuccess) return berr;
-    if (!buf) return launch(h, true, P, st);
-    uint32_t* cont = reinterpret_cast<uint32_t*>((char*)buf + rec_bytes);
-    if (hipError_t e = hipMemsetAsync(cont, 0, hdr * sizeof(uint32_t), st)) return e;
-    const int team = split_tr > 0 ? (int)std::min<long long>(P.B, TEAM_CAP) : 0;
-    KP P1 = P;
-    P1.ckpt_it = split_it > 0 ? split_it : 0;
-    P1.ckpt_tr = split_tr;
-    P1.team = team;
-    P1.ckpt = (double*)buf;
-    P1.cont = cont;
-    if (hipError_t e = launch(h, true, P1, st)) return e;
-    KP P2 = P;   // single records, and team records
-    P2.resume = pair && h->split_pair && team == 0 && cf.precision != ALIPMPC_PREC_FP32 ? 2 : 1;
-    P2.team = team;
-    P2.ckpt = (double*)buf;
-    P2.cont = cont;
-    return launch(h, true, P2, st);
+    SpFacts f{};
+    f.program = prog;
+    f.resto_ipopt = h->cfg.restoration == ALIPMPC_RESTORATION_IPOPT && prog != SP_PROG_DD;
+    f.B = B;
+    if (prog == SP_PROG_WAVE_F64 || prog == SP_PROG_WAVE_F32) {   // (the programs whose plan reads them)
+        f.slots = resident_slots(h);
+        if (f.resto_ipopt && prog == SP_PROG_WAVE_F64) f.slots_resto = resident_slots(h, true);
+    }
+    f.split_it = split_it;
+    f.split_tr = split_tr;
+    f.split_pair = h->split_pair;
+    f.allow_pair = pair;
+    f.ordered = ordered;
+    return f;
+}
+
+// the buffers of one solve: the stream's records and their counters (a split launch) and its hand-off list, which the
+// plan's ZERO_LIST step takes
+struct SolveBufs {
+    void* rec = nullptr;
+    uint32_t* cont = nullptr;
+    size_t hdr_bytes = 0;
+    uint32_t* list = nullptr;
+};
+
+// one step of a solve's plan; P: the caller's parameters
+static hipError_t issue_step(const Handle* h, const SpStep& s, const KP& P, hipStream_t st, SolveBufs& b)
+{
+    const bool f32 = h->cfg.precision == ALIPMPC_PREC_FP32, modi = h->cfg.variant == ALIPMPC_VARIANT_MODI;
+    switch (s.kind) {
+    case SP_ZERO_HEADER: return hipMemsetAsync(b.cont, 0, b.hdr_bytes, st);
+    case SP_ZERO_LIST:
+        if (hipError_t e = redo_list(h, st, P.B, &b.list)) return e;
+        return hipMemsetAsync(b.list, 0, sizeof(uint32_t), st);
+    case SP_DD:
+        return with_n(h->N, hipErrorInvalidValue,
+                      [&](auto n) { return launch_dd<decltype(n)::value>(true, P, smem_bytes(h, true), st); });
+    case SP_SENS:
+    case SP_SENS_OBS:
+        return with_n(h->N, hipErrorInvalidValue, [&](auto n) {
+            return launch_sens<decltype(n)::value>(s.kind == SP_SENS_OBS, s.resto, P, smem_bytes(h, true), st);
+        });
+    case SP_LANE: {   // (with a list: an instance whose line search fails is listed, lane_solve.inc)
+        KP K = P;
+        K.redo = b.list;
+        return f32 ? launch_lane<float>(h->lane_nct, modi, K, st) : launch_lane<double>(h->lane_nct, modi, K, st);
+    }
+    case SP_WAVE: {   // (phase 1 of a split launch starts the list and phase 2 continues it)
+        KP K = P;
+        K.redo = b.list;
+        K.ckpt_it = s.ckpt_it;
+        K.ckpt_tr = s.ckpt_tr;
+        K.team = s.team;
+        K.resume = s.phase == 2 ? (s.form == SP_PAIR ? 2 : 1) : 0;
+        K.ckpt = s.phase ? (double*)b.rec : nullptr;
+        K.cont = s.phase ? b.cont : nullptr;
+        return with_n(h->N, hipErrorInvalidValue, [&](auto n) {
+            return launch_wave<decltype(n)::value>(f32, s.resto, s.form, K, smem_bytes(h, true), st);
+        });
+    }
+    case SP_HANDOFF: {   // slot k of the fp64 work queue solves list[1 + k], k < list[0], on the same stream and queue pair
+        KP K = P;
+        K.order = reinterpret_cast<const int32_t*>(b.list + 1);
+        K.bcount = b.list;
+        return with_n(h->N, hipErrorInvalidValue, [&](auto n) {
+            return launch_wave<decltype(n)::value>(false, s.resto, s.form, K, smem_bytes(h, true, 1), st);
+        });
+    }
+    }
+    return hipErrorInvalidValue;
+}
+
+// Every solve of the library: the facts, the buffers, the plan (solve_plan.inc), its steps in order.
+static hipError_t launch_solve(Handle* h, const KP& P, hipStream_t st, SpProgram prog, int split_it = 0, int split_tr = 0,
+                               bool pair = false)
+{
+    SpFacts f = solve_facts(h, prog, P.B, P.order != nullptr, split_it, split_tr, pair);
+    SolveBufs b;
+    if (sp_splits(f)) {
+        // records for the slots, not for this B: the buffer of a stream never changes size
+        const size_t rec_bytes = ((size_t)f.slots * ckpt_doubles(h->mo4) * sizeof(double) + 255) & ~(size_t)255;
+        // (the counters, then instance ids and the two class lists of the single records)
+        const size_t need = rec_bytes + ((size_t)cont_hdr(f.slots) + (size_t)CONT_WORDS_PER_SLOT * (size_t)f.slots) * sizeof(uint32_t);
+        hipError_t berr = hipSuccess;
+        b.rec = split_buffer(h, st, need, berr);
+        if (berr != hipSuccess) return berr;
+        b.cont = reinterpret_cast<uint32_t*>((char*)b.rec + rec_bytes);
+        b.hdr_bytes = (size_t)cont_hdr(f.slots) * sizeof(uint32_t);
+    }
+    f.records = b.rec != nullptr;
+    for (const SpStep& s : solve_plan(f))
+        if (hipError_t e = issue_step(h, s, P, st, b)) return e;
+    return hipSuccess;
 }
 
 static int run_batch(Handle* h, bool solve, int64_t B, const double* x0, const double* goal, const int8_t* leg,
@@ -1083,7 +1059,7 @@ static int run_batch(Handle* h, bool solve, int64_t B, const double* x0, const d
     if (int e = S.commit()) return e;
     TimedSpan span{h, S.st};
     if (int e = span.begin()) return e;
-    HIPCHK(h, solve ? launch_solve(h, P, S.st, h->split_it, h->split_tr, true) : launch(h, false, P, S.st));
+    HIPCHK(h, solve ? launch_solve(h, P, S.st, program_of(h), h->split_it, h->split_tr, true) : launch_eval_hook(h, P, S.st));
     if (int e = span.end()) return e;
     return S.finish();
 }
@@ -1097,22 +1073,9 @@ int alipmpc_solve_batch(void* handle, int64_t B, const double* x0, const double*
                      iters, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, hip_stream);
 }
 
-// the sensitivity build's launch of a handle in its domain (fp64 wave program, N <= 5); P carries dfoot, du and sens_ok
-// in grad_out, J_out and active_out; obs: the obstacle-sensitivity build, with dfoot_obs and du_obs in c_out and cl_out
-static hipError_t launch_sens(Handle* h, const KP& P, hipStream_t st, bool obs = false)
-{
-    const size_t smem = smem_bytes(h, true);
-    switch (h->N) {
-    case 1: return launch_sens_1(P, smem, st, obs);
-    case 2: return launch_sens_2(P, smem, st, obs);
-    case 3: return launch_sens_3(P, smem, st, obs);
-    case 4: return launch_sens_4(P, smem, st, obs);
-    case 5: return launch_sens_5(P, smem, st, obs);
-    }
-    return hipErrorInvalidValue;
-}
-
-// the calls of alipmpc_solve_sens_batch and alipmpc_solve_sens_obs_batch (obs)
+// the calls of alipmpc_solve_sens_batch and alipmpc_solve_sens_obs_batch (obs): a handle in the sensitivity build's domain
+// (fp64 wave program, N <= 5); P carries dfoot, du and sens_ok in grad_out, J_out and active_out, and the
+// obstacle-sensitivity build's dfoot_obs and du_obs in c_out and cl_out
 static int run_sens(Handle* h, bool obs, int64_t B, const double* x0, const double* goal, const int8_t* leg,
                     const double* cir, const int32_t* nc, const double* elp, const int32_t* ne, const double* u0,
                     double* u_out, double* foot_out, double* x_pred, int32_t* status, int32_t* iters, double* dfoot,
@@ -1162,7 +1125,7 @@ static int run_sens(Handle* h, bool obs, int64_t B, const double* x0, const doub
     P.cl_out = d_duo;
     TimedSpan span{h, S.st};
     if (int e = span.begin()) return e;
-    HIPCHK(h, launch_sens(h, P, S.st, obs));
+    HIPCHK(h, launch_solve(h, P, S.st, obs ? SP_PROG_SENS_OBS : SP_PROG_SENS));
     if (int e = span.end()) return e;
     return S.finish();
 }
@@ -1265,7 +1228,7 @@ int alipmpc_rollout_batch(void* handle, int64_t B, int32_t S, const double* x0, 
     TimedSpan span{h, st};
     if (int e = span.begin()) return e;
     for (int t = 0; t < S; ++t) {
-        HIPCHK(h, launch(h, true, P, st));
+        HIPCHK(h, launch_solve(h, P, st, program_of(h)));
         A.t = t;
         hipLaunchKernelGGL(advance_kernel, dim3(g1), dim3(256), 0, st, A);
         HIPCHK(h, hipGetLastError());
@@ -1648,13 +1611,7 @@ int alipmpc_solve_slots(void* handle, int64_t* slots)
     Handle* h = (Handle*)handle;
     if (!h || !slots) return fail(h, ALIPMPC_EINVAL, "null argument");
     HIPCHK(h, hipSetDevice(h->device));
-    unsigned res = 0;
-    KP P = make_kp(h, 1, true);
-    HIPCHK(h, launch(h, true, P, h->own, &res));
-    if (h->lane_nct >= 0)
-        *slots = (int64_t)res * (h->cfg.precision == ALIPMPC_PREC_FP32 ? lane::lanes_of<float>() : lane::lanes_of<double>());
-    else
-        *slots = (int64_t)res * WAVES_PER_BLOCK;
+    *slots = resident_slots(h);
     return ALIPMPC_OK;
 }
 
@@ -1682,12 +1639,17 @@ int alipmpc_solve_launches(void* handle, int64_t B, int32_t* launches, int32_t* 
 {
     Handle* h = (Handle*)handle;
     if (!h || !launches || !team) return fail(h, ALIPMPC_EINVAL, "null argument");
-    int64_t slots = 0;
-    if (int rc = alipmpc_solve_slots(handle, &slots)) return rc;
-    // launch_solve's conditions for the split form (no order / active mask on the batch API)
-    const bool split = split_form(h, B, h->split_it, h->split_tr, slots);
-    *launches = split ? 2 : 1;
-    *team = split && h->split_tr > 0 && h->cfg.precision != ALIPMPC_PREC_FP32 ? TEAM_WAVES : 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    // the plan of a batch solve on a stream with a record buffer (no launch order on the batch API): its launches other
+    // than the hand-off's
+    SpFacts f = solve_facts(h, program_of(h), B, false, h->split_it, h->split_tr, true);
+    f.records = true;
+    *launches = 0;
+    *team = 1;
+    for (const SpStep& s : solve_plan(f)) {
+        if (sp_is_launch(s.kind) && s.kind != SP_HANDOFF) ++*launches;
+        if (s.kind == SP_WAVE && s.form == SP_TEAM) *team = TEAM_WAVES;
+    }
     return ALIPMPC_OK;
 }
 
